@@ -22,7 +22,13 @@ Modes (--mode):
                RGBA f32 frame (16 B/px) or writeColorImage's bytes (RGBA8,
                4 B/px, encoded in the eye pass's epilogue).
 
-Whatever the mode, the line also carries `tile_gather`: the strong-scaling
+A plain run sets up, warms up, times the steps, writes the last step's frames when
+--dump-outputs names a directory, and prints the line.  --full adds the secondary
+measurements to the same line: the one-lane kernel pass and the rooflines, the
+fused-shadow frames, `tile_gather`, `host_output` and `cpu_baseline` (each still
+dropped by its own --no-* option).
+
+With --full, whatever the mode, the line also carries `tile_gather`: the strong-scaling
 tile-partitioned frame (the north star's assembled framebuffer) measured in the
 same run for RGBA f32 and RGBA8, so every N of a scaling sweep reports both the
 weak (frames) and the strong (tile-gather) figure.  With --dist-backend gloo
@@ -82,7 +88,16 @@ def parse():
     ap.add_argument("--preroll-ms", type=float, default=300.0)
     ap.add_argument("--no-host-output", action="store_true",
                     help="skip the secondary host-output (PCIe-inclusive drop-in) measurement")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (one-lane kernel pass and rooflines, fused-shadow "
+                         "frames, tile-gather, host output, CPU baseline); the --no-* options then drop single ones")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="frames mode: after the timed steps, write frames of the last timed step as "
+                         "DIR/frame_<animation frame>.npy (float32; a seeded pixel sample of frames too large)")
+    a = ap.parse_args()
+    if a.dump_outputs and a.mode != "frames":
+        ap.error("--dump-outputs writes the frames of --mode frames")
+    return a
 
 
 FORMATS = {"rgba32f": 0, "rgba8": 1}
@@ -354,6 +369,41 @@ def host_output(rtm, scene, eye, shadow, W, H, K, flags, frames=8, n_gpus=0):
     return res
 
 
+DUMP_FRAMES = 4  # frames of the last timed step that --dump-outputs writes
+DUMP_BYTES = 48 << 20  # all of them together stay below this
+DUMP_SEED = 20180
+
+
+def dump_outputs(path, ring, slot, n_timed, frames_per_step, frame_id, W, H):
+    """--dump-outputs: what a caller of the timed call holds after its last step.  Timed
+    frame i went to ring[slot(i)], so the last min(frames_per_step, len(ring)) frames are
+    still there: up to DUMP_FRAMES of them, evenly spaced and the last one among them, go to
+    path/frame_<frame_id(i)>.npy as float32 -- (H, W, 4) whole when they fit DUMP_BYTES
+    together, else the same seeded sample of pixels of each, (n, 4) in ascending pixel
+    order.  Returns what was written, for the result line."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    alive = min(frames_per_step, len(ring), n_timed)
+    k = min(DUMP_FRAMES, alive)
+    picks = sorted(n_timed - 1 - (j * alive) // k for j in range(k))
+    n_px = DUMP_BYTES // (16 * max(len(picks), 1))
+    idx = None
+    if n_px < W * H:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(W * H, size=n_px, replace=False))
+        idx = torch.from_numpy(idx).to(ring[0].device)
+    names = []
+    for i in picks:
+        frame = ring[slot(i)]
+        arr = (frame if idx is None else frame.view(W * H, 4)[idx]).cpu().numpy()
+        names.append(f"frame_{frame_id(i):06d}")
+        np.save(os.path.join(path, names[-1] + ".npy"), arr)
+    return {"dir": path, "arrays": names, "dtype": "float32",
+            "pixels_per_frame": W * H if idx is None else n_px,
+            "sample": None if idx is None else f"numpy default_rng({DUMP_SEED}).choice({W * H}, {n_px}), sorted"}
+
+
 def librtm_build_id() -> str:
     """sha256 (first 16 hex digits) of the librtm.so this run loads: the build a PMC
     summary must have profiled for its counters to describe the benched code."""
@@ -616,7 +666,7 @@ def main():
             preroll_frames += 50
         preroll["ms"], preroll["frames"] = round((time.perf_counter() - t_pre) * 1e3, 1), preroll_frames
         tg_primary = tile_gather(rtm, lib, ctx, group, world, rank, dist, tdev, c_scenes, eye, shadow, W, H, K,
-                                 flags, fmt, nS, nW, bands=True)
+                                 flags, fmt, nS, nW, bands=a.full)
         tile_scaling({a.format: tg_primary}, {}, world)  # (root ingress; no one-GPU rate in this mode)
         elapsed = tg_primary["ms_per_step"] * nS / 1e3
     else:
@@ -639,6 +689,14 @@ def main():
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
 
+    # the last step's frames, before a secondary pass writes the ring again; every rank
+    # writes its own (frames mode: timed frame i of rank r is animation frame (nW + i) * N + r)
+    dumped = None
+    if a.dump_outputs:
+        # (timed frame i's ring slot: the one call counts from 0, the per-frame calls go on from the warmup)
+        dumped = dump_outputs(a.dump_outputs, ring, (lambda i: i % n_ring) if sequence else (lambda i: (nW + i) % n_ring),
+                              nS, F, lambda i: (nW + i) * world + rank, W, H)
+
     # the shadow map's storage in the timed frames (coded: 1-2 B per texel; fused: none).
     # A frame without shadow raster and march (config 7, main()'s scene) has an all-+INF
     # shadow viewport: the library runs no shadow pass and its eye pass evaluates the
@@ -650,7 +708,7 @@ def main():
     # per-kernel HIP-event durations over the timed region (ctx stream)
     n_launches = nS
     sh_ms, eye_ms = ctx.kernel_ms_history((n_launches + timing_stride - 1) // timing_stride)
-    if tile_mode:  # the group's own contexts ran the bands: one timed pass of rank 0's band on ctx
+    if tile_mode and a.full:  # the group's own contexts ran the bands: one timed pass of rank 0's band on ctx
         ctx.set_timing_capacity(1)
         r0, r1 = shard.row_band(H, world, rank)
         if r1 > r0:
@@ -682,6 +740,7 @@ def main():
         avg = lambda v: sum(v) / max(len(v), 1)
         in_lanes = {"lanes": lanes, "shadow_pass_ms": round(avg(sh_ms), 5), "eye_pass_ms": round(avg(eye_ms), 5),
                     "note": "HIP-event kernel durations in the timed region, kernels of other lanes alongside"}
+    if lanes > 1 and a.full:
         n1 = min(nS, 400)
         ctx.set_lanes(1)
         ctx.render_frames_async([0] * min(nW, F), eye, shadow, W, H, K, flags, outp[:min(nW, F)],
@@ -710,7 +769,7 @@ def main():
     # texels the eye pass looks up instead of materialising the whole shadow map.
     # Bit-identical image (tests/test_gpu_parity.py::test_fused_shadow_identical).
     alt_fused = None
-    if sequence and not a.no_alt and not fused and not trivial:
+    if a.full and sequence and not a.no_alt and not fused and not trivial:
         fflags = flags | rtm.abi.RTM_FLAG_FUSED_SHADOW
         ctx.set_timing_capacity(max(1, nS // timing_stride))
         ctx.render_frames_async([0] * min(nW, F), eye, shadow, W, H, K, fflags, outp[:min(nW, F)],
@@ -740,60 +799,63 @@ def main():
         value = pixels / elapsed / 1e6
         s0 = scenes[nW] if nW < len(scenes) else scenes[0]
         band_h = rows[1] - rows[0]
-        st = ctx.stats(s0, eye, shadow, W, H, K, flags)
-        sep = metrics.shared_z_separable(shadow)
-        def frame_work(fused_):
-            return metrics.frame_work(st, W, H, len(s0.spherePrimitives), len(s0.patches), flags, fused=fused_,
-                                      sep=sep, n_planes=len(s0.circlePlanePrimitives),
-                                      n_cyls=len(s0.cappedCylinderPrimitives),
-                                      perspective=eye.type_ == sc.PERSPECTIVE,
-                                      search=sep,
-                                      n_sdfs=len(s0.sdfPrimitives), map_texel_bytes=map_bytes,
-                                      map_stored_bytes=map_stored if map_stored else None,
-                                      span_records=span_records,
-                                      moving=(shadow.dirNormalized[0] * 0.03 != 0.0
-                                              or shadow.dirNormalized[1] * 0.03 != 0.0))
+        # the rooflines need a statistics pass of their own and the one-lane kernel times: --full
+        roof, roof_other, roof_frame = None, None, None
+        if a.full:
+            st = ctx.stats(s0, eye, shadow, W, H, K, flags)
+            sep = metrics.shared_z_separable(shadow)
+            def frame_work(fused_):
+                return metrics.frame_work(st, W, H, len(s0.spherePrimitives), len(s0.patches), flags, fused=fused_,
+                                          sep=sep, n_planes=len(s0.circlePlanePrimitives),
+                                          n_cyls=len(s0.cappedCylinderPrimitives),
+                                          perspective=eye.type_ == sc.PERSPECTIVE,
+                                          search=sep,
+                                          n_sdfs=len(s0.sdfPrimitives), map_texel_bytes=map_bytes,
+                                          map_stored_bytes=map_stored if map_stored else None,
+                                          span_records=span_records,
+                                          moving=(shadow.dirNormalized[0] * 0.03 != 0.0
+                                                  or shadow.dirNormalized[1] * 0.03 != 0.0))
 
-        work = frame_work(fused or trivial)
-        if alt_fused is not None and band_h == H:
-            # the fused frame is one kernel (the eye pass evaluating the shadow texels its
-            # hit pixels read): its algorithmic bytes and ops per frame over its wall time
-            # per frame in the same run
-            rf = dict(metrics.roofline("eye_pass", frame_work(True), alt_fused["ms_per_frame"]))
-            rf.pop("traffic", None)
-            rf["kernel"] = "frame (fused shadow: one eye-pass kernel per frame)"
-            rf["note"] = ("algorithmic bytes per frame (16 B/px store, no map) / wall time per frame "
-                          f"of the alt_fused_shadow run ({alt_fused['lanes']} lanes); PMC: profiles/*pmc_fused*")
-            alt_fused["roofline_frame"] = rf
-        if band_h != H:  # rank 0 renders one band: scale the frame's work to it (approximate)
-            for kk in work.values():
-                kk["ops"] = int(kk["ops"] * band_h / H)
-                kk["bytes"] = int(kk["bytes"] * band_h / H)
-        # the whole frame (both passes' algorithmic bytes) over the headline time per frame
-        passes = [work[k] for k in ("shadow_pass", "eye_pass") if k in work]
-        work["frame"] = {"ops": sum(w["ops"] for w in passes), "bytes": sum(w["bytes"] for w in passes)}
-        roof_frame = dict(metrics.roofline("frame", work, elapsed / nS * 1e3))  # per GPU
-        roof_frame.pop("traffic", None)
-        roof_frame["note"] = ("both passes' algorithmic bytes per frame / wall time per frame of the timed region"
-                              + (f" ({lanes} lanes)" if lanes > 1 else ""))
-        # the kernel rooflines are per LAUNCH (what rocprofv3 and the PMC passes see): a
-        # launch of B frames (rtm_ctx_set_batch) moves B frames' bytes in its duration
-        nb = max(launch_batch, 1)
-        work_l = {k: {"ops": v["ops"] * nb, "bytes": v["bytes"] * nb} for k, v in work.items()}
+            work = frame_work(fused or trivial)
+            if alt_fused is not None and band_h == H:
+                # the fused frame is one kernel (the eye pass evaluating the shadow texels its
+                # hit pixels read): its algorithmic bytes and ops per frame over its wall time
+                # per frame in the same run
+                rf = dict(metrics.roofline("eye_pass", frame_work(True), alt_fused["ms_per_frame"]))
+                rf.pop("traffic", None)
+                rf["kernel"] = "frame (fused shadow: one eye-pass kernel per frame)"
+                rf["note"] = ("algorithmic bytes per frame (16 B/px store, no map) / wall time per frame "
+                              f"of the alt_fused_shadow run ({alt_fused['lanes']} lanes); PMC: profiles/*pmc_fused*")
+                alt_fused["roofline_frame"] = rf
+            if band_h != H:  # rank 0 renders one band: scale the frame's work to it (approximate)
+                for kk in work.values():
+                    kk["ops"] = int(kk["ops"] * band_h / H)
+                    kk["bytes"] = int(kk["bytes"] * band_h / H)
+            # the whole frame (both passes' algorithmic bytes) over the headline time per frame
+            passes = [work[k] for k in ("shadow_pass", "eye_pass") if k in work]
+            work["frame"] = {"ops": sum(w["ops"] for w in passes), "bytes": sum(w["bytes"] for w in passes)}
+            roof_frame = dict(metrics.roofline("frame", work, elapsed / nS * 1e3))  # per GPU
+            roof_frame.pop("traffic", None)
+            roof_frame["note"] = ("both passes' algorithmic bytes per frame / wall time per frame of the timed region"
+                                  + (f" ({lanes} lanes)" if lanes > 1 else ""))
+            # the kernel rooflines are per LAUNCH (what rocprofv3 and the PMC passes see): a
+            # launch of B frames (rtm_ctx_set_batch) moves B frames' bytes in its duration
+            nb = max(launch_batch, 1)
+            work_l = {k: {"ops": v["ops"] * nb, "bytes": v["bytes"] * nb} for k, v in work.items()}
 
-        def kroof(kernel, ms_per_frame):
-            fpl = nb if kernel in ("eye_pass", "shadow_pass") else 1
-            r = dict(metrics.roofline(kernel, work_l, ms_per_frame * nb, _latest_traffic(a.config, kernel, fpl)))
-            r["frames_per_launch"] = nb
-            r["pmc"] = pmc_fractions(a.config, kernel, fpl, work_l[kernel]["ops"])
-            return r
+            def kroof(kernel, ms_per_frame):
+                fpl = nb if kernel in ("eye_pass", "shadow_pass") else 1
+                r = dict(metrics.roofline(kernel, work_l, ms_per_frame * nb, _latest_traffic(a.config, kernel, fpl)))
+                r["frames_per_launch"] = nb
+                r["pmc"] = pmc_fractions(a.config, kernel, fpl, work_l[kernel]["ops"])
+                return r
 
-        dom = "eye_pass" if (fused or trivial or avg_eye >= avg_sh) else "shadow_pass"
-        dom_ms = avg_eye if dom == "eye_pass" else avg_sh
-        roof = kroof(dom, dom_ms)
-        other = "shadow_pass" if dom == "eye_pass" else "eye_pass"
-        other_ms = avg_sh if other == "shadow_pass" else avg_eye
-        roof_other = kroof(other, other_ms) if other_ms > 0 and not trivial else None
+            dom = "eye_pass" if (fused or trivial or avg_eye >= avg_sh) else "shadow_pass"
+            dom_ms = avg_eye if dom == "eye_pass" else avg_sh
+            roof = kroof(dom, dom_ms)
+            other = "shadow_pass" if dom == "eye_pass" else "eye_pass"
+            other_ms = avg_sh if other == "shadow_pass" else avg_eye
+            roof_other = kroof(other, other_ms) if other_ms > 0 and not trivial else None
         res = {
             "metric": cfg.get("metric", METRIC if a.config <= 5 else METRIC_F1 if a.config <= 7 else METRIC_F4),
             "value": round(value, 2),
@@ -819,8 +881,11 @@ def main():
                        "parallelism": (f"frame-parallel x{world}" if not tile_mode
                                        else f"row-bands x{world} + one gather ({a.format})"),
                        "rows_rank0": band_h},
-            "kernels": {"shadow_pass_ms": round(avg_sh, 5), "eye_pass_ms": round(avg_eye, 5),
-                        "frame_kernel_ms": round(avg_sh + avg_eye, 5)},
+            # (per kernel alone on the chip: with several lanes, or the group's own contexts,
+            # that is a pass of its own and comes with --full; `kernels_in_lanes` is the timed region's)
+            "kernels": ({"shadow_pass_ms": round(avg_sh, 5), "eye_pass_ms": round(avg_eye, 5),
+                         "frame_kernel_ms": round(avg_sh + avg_eye, 5)}
+                        if a.full or (lanes == 1 and not tile_mode) else None),
             "roofline": roof,
             "roofline_other_kernel": roof_other,
             "roofline_frame": roof_frame,
@@ -835,6 +900,8 @@ def main():
             "alt_fused_shadow": alt_fused,
             "tile_gather": tg_primary if tile_mode else None,
             "host_output": None,
+            "full": a.full,
+            "dumped_outputs": dumped,
             "parity": ("bit-exact vs CPU oracle (tests/test_gpu_parity.py)" if a.config <= 5
                        else "bit-exact vs CPU oracle (tests/test_raytrace.py)" if a.config <= 8
                        else "bit-exact vs CPU oracle (tests/test_general_march.py)"),
@@ -842,7 +909,7 @@ def main():
 
     # Secondary: the tile-partitioned, gathered frame (strong scaling) in RGBA f32 and RGBA8
     tile = None
-    if not tile_mode and a.tile_gather_steps != 0:
+    if a.full and not tile_mode and a.tile_gather_steps != 0:
         tile = {}
         # a watchdog for the secondary measurement: RCCL over several ranks is exercised
         # here for the first time in a run; if it stalls, rank 0 still prints the line
@@ -883,7 +950,7 @@ def main():
             if res is not None:
                 res["group_close_error"] = str(ex)[:300]
 
-    if world > 1 and not a.no_host_output and a.config in (3, 4):
+    if a.full and world > 1 and not a.no_host_output and a.config in (3, 4):
         # the N-link host frame: rank 0 drives all N devices while the others wait
         barrier()
         if rank == 0:
@@ -897,9 +964,9 @@ def main():
                 res["host_output"] = {"skipped": f"{torch.cuda.device_count()} visible devices < {world} ranks"}
         barrier()
     if rank == 0:
-        if world == 1 and not a.no_host_output and a.config == 3:
+        if a.full and world == 1 and not a.no_host_output and a.config == 3:
             res["host_output"] = host_output(rtm, scenes[0], eye, shadow, W, H, K, cfg["flags"])
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             what = ("Scene A-bench frame 100" if a.config in (2, 3, 4) else cfg["desc"].split(", ", 1)[1])
             res["cpu_baseline"] = cpu_baseline(s0, eye, shadow, W, H, K, flags, a.cpu_threads, what)
         print(json.dumps(res), flush=True)

@@ -104,7 +104,7 @@ def test_bench_tile_gather_gloo_rehearsal_world2(fmt):
     """bench.py --mode tile-gather end to end with two ranks sharing the box's GPU
     (gloo gathers the CPU-staged bands; the 8-GPU run uses RCCL): one JSON line,
     strong scaling, both ranks' pixels counted once."""
-    res = _run_bench(["--gpus", "2", "--dist-backend", "gloo", "--mode", "tile-gather", "--format", fmt,
+    res = _run_bench(["--full", "--gpus", "2", "--dist-backend", "gloo", "--mode", "tile-gather", "--format", fmt,
                       "--config", "2", "--steps", "3", "--warmup", "1", "--frames-per-step", "2", "--preroll-ms", "0", "--no-cpu-baseline",
                       "--no-alt"], 2)
     assert res["n_gpus"] == 2 and res["scaling"] == "strong" and res["value"] > 0
@@ -116,7 +116,7 @@ def test_bench_tile_gather_gloo_rehearsal_world2(fmt):
 @pytest.mark.gpu
 def test_bench_frames_gloo_rehearsal_world2_carries_tile_gather():
     """The default (frames) mode with two ranks also reports the tile-gather figures."""
-    res = _run_bench(["--gpus", "2", "--dist-backend", "gloo", "--config", "2", "--steps", "20", "--warmup", "5",
+    res = _run_bench(["--full", "--gpus", "2", "--dist-backend", "gloo", "--config", "2", "--steps", "20", "--warmup", "5",
                       "--frames-per-step", "64", "--preroll-ms", "20", "--tile-gather-steps", "4", "--no-cpu-baseline",
                       "--no-alt"], 2)
     assert res["scaling"] == "weak" and res["n_gpus"] == 2

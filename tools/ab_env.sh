@@ -11,7 +11,7 @@ for c in $CFGS; do for r in $(seq 1 "$ROUNDS"); do for vi in "${!VA[@]}"; do
   v=${VA[$vi]}
   f="$O/b${c}_v${vi}_r$r.log"
   if [ "$v" = "-" ]; then envs=(); else read -ra envs <<< "$v"; fi
-  env "${envs[@]}" timeout -k 10 150 python -u bench.py --config "$c" --no-cpu-baseline --no-alt --tile-gather-steps 0 --no-host-output $EXTRA > "$f" 2>&1
+  env "${envs[@]}" timeout -k 10 150 python -u bench.py --full --config "$c" --no-cpu-baseline --no-alt --tile-gather-steps 0 --no-host-output $EXTRA > "$f" 2>&1
   rc=$?; [ $rc -ne 0 ] && { tail -5 "$f"; exit $rc; }
   python - "$f" "$c" "$v" <<'PY'
 import json, sys
