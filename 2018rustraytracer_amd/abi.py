@@ -12,10 +12,11 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # RTM_LIB: another build of the same library (A/B timing runs only, tools/ab_bench.py)
 LIB_PATH = os.environ.get("RTM_LIB") or os.path.join(_PKG_DIR, "librtm.so")
 
-RTM_ABI_VERSION = 11
+RTM_ABI_VERSION = 12
 # library versions whose public structs share this layout (an RTM_LIB A/B build may be one)
-RTM_ABI_LAYOUT_COMPATIBLE = frozenset({9, 10, 11})
+RTM_ABI_LAYOUT_COMPATIBLE = frozenset({9, 10, 11, 12})
 RTM_MAX_SPHERES = 16
+RTM_MAX_SCENE_SPHERES = 65536  # the binned sphere path (ABI v12)
 RTM_MAX_PATCHES = 4
 RTM_MAX_CIRCLE_PLANES = 16
 RTM_MAX_CAPPED_CYLINDERS = 16
@@ -144,6 +145,10 @@ ABI_SYMBOLS = [
     ("rtm_ctx_shadow_map_stored_bytes", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(_I32)]),
     ("rtm_ctx_frames_plan", C.c_int, [_P, _I32, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     ("rtm_ctx_last_eye_blocks", C.c_int, [_P, C.POINTER(_I32)]),
+    ("rtm_ctx_last_sphere_path", C.c_int, [_P, C.POINTER(_I32)]),
+    ("rtm_ctx_last_bin_refs", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("rtm_bin_plan", C.c_int, [C.POINTER(rtm_scene), C.POINTER(rtm_camera), _I32, _I32, C.POINTER(_I32),
+                               C.POINTER(_I32), C.POINTER(_I32), C.c_int64, C.POINTER(C.c_int64)]),
     ("rtm_render_multi", C.c_int, [C.POINTER(rtm_scene), C.POINTER(rtm_camera), C.POINTER(rtm_camera),
                                    _I32, _I32, _I32, _I32, C.POINTER(C.c_float), _I32]),
     ("rtm_render_stats", C.c_int, [_P, C.POINTER(rtm_scene), C.POINTER(rtm_camera),

@@ -14,7 +14,9 @@
 #include <cstring>
 #include <ctime>
 #include <memory>
+#include <new>
 #include <string>
+#include <system_error>
 #include <thread>
 #include <limits>
 #include <vector>
@@ -299,10 +301,13 @@ PatchK patch_k(const rtm_patch& p) {
     return k;
 }
 
-int validate_scene(const rtm_scene* scene) {
+// many_ok: the caller has the binned sphere path (more than RTM_MAX_SPHERES spheres, up to
+// RTM_MAX_SCENE_SPHERES, beside patches only); every other caller answers such a scene
+// with RTM_ERR_UNSUPPORTED -- after the checks that make a scene invalid anywhere.
+int validate_scene(const rtm_scene* scene, bool many_ok = false) {
     if (!scene) return fail(RTM_ERR_INVALID, "scene is NULL");
-    if (scene->n_spheres < 0 || scene->n_spheres > RTM_MAX_SPHERES)
-        return fail(RTM_ERR_INVALID, "n_spheres=%d outside [0,%d]", scene->n_spheres, RTM_MAX_SPHERES);
+    if (scene->n_spheres < 0 || scene->n_spheres > RTM_MAX_SCENE_SPHERES)
+        return fail(RTM_ERR_INVALID, "n_spheres=%d outside [0,%d]", scene->n_spheres, RTM_MAX_SCENE_SPHERES);
     if (scene->n_patches < 0 || scene->n_patches > RTM_MAX_PATCHES)
         return fail(RTM_ERR_INVALID, "n_patches=%d outside [0,%d]", scene->n_patches, RTM_MAX_PATCHES);
     if (scene->n_spheres > 0 && !scene->spheres) return fail(RTM_ERR_INVALID, "spheres is NULL");
@@ -338,8 +343,21 @@ int validate_scene(const rtm_scene* scene) {
         if (scene->sdfs[i].max_steps < 0)
             return fail(RTM_ERR_INVALID, "sdf %d has max_steps=%d", i, scene->sdfs[i].max_steps);
     }
+    if (scene->n_spheres > RTM_MAX_SPHERES) {
+        if (!many_ok)
+            return fail(RTM_ERR_UNSUPPORTED,
+                        "n_spheres=%d: more than RTM_MAX_SPHERES (%d) spheres render only through rtm_render_ex, "
+                        "rtm_render_async, rtm_render_rows_async and rtm_render_frames_async",
+                        scene->n_spheres, RTM_MAX_SPHERES);
+        if (np > 0 || nc > 0 || ns > 0)
+            return fail(RTM_ERR_UNSUPPORTED,
+                        "n_spheres=%d: more than RTM_MAX_SPHERES (%d) spheres render beside patches only "
+                        "(no circle planes, capped cylinders or SDFs)", scene->n_spheres, RTM_MAX_SPHERES);
+    }
     return RTM_OK;
 }
+
+inline bool many_spheres(const rtm_scene* scene) { return scene && scene->n_spheres > RTM_MAX_SPHERES; }
 
 
 bool build_rt(const rtm_scene* scene, const rtm_camera* eye, RtK& k);
@@ -528,10 +546,10 @@ int validate_dims(int32_t w, int32_t h) {
 // check of a whole call's frames: a full build per frame there cost the group path a
 // second build of every frame before its first launch).
 int validate_frame(const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow, int32_t W, int32_t H,
-                   int32_t steps, int32_t flags) {
+                   int32_t steps, int32_t flags, bool many_ok = false) {
     int rc;
-    if ((rc = validate_scene(scene)) || (rc = validate_camera(eye, "eye")) || (rc = validate_camera(shadow, "shadow")) ||
-        (rc = validate_dims(W, H)))
+    if ((rc = validate_scene(scene, many_ok)) || (rc = validate_camera(eye, "eye")) ||
+        (rc = validate_camera(shadow, "shadow")) || (rc = validate_dims(W, H)))
         return rc;
     if (steps < 0) return fail(RTM_ERR_INVALID, "march_steps=%d < 0", steps);
     if (flags & ~(RTM_FLAG_NO_MARCH | RTM_FLAG_NO_SHADOW_RASTER | RTM_FLAG_FUSED_SHADOW))
@@ -540,7 +558,53 @@ int validate_frame(const rtm_scene* scene, const rtm_camera* eye, const rtm_came
     // shadow lookup; the eye may be PERSPECTIVE (spheres via project_sphere_persp, row f-3).
     if (shadow->type != RTM_CAMERA_ORTHOGONAL)
         return fail(RTM_ERR_UNSUPPORTED, "frame path needs an ORTHOGONAL shadow camera");
+    if (many_spheres(scene) && eye->type != RTM_CAMERA_ORTHOGONAL)
+        return fail(RTM_ERR_UNSUPPORTED, "n_spheres=%d: more than RTM_MAX_SPHERES (%d) spheres need an ORTHOGONAL eye camera",
+                    scene->n_spheres, RTM_MAX_SPHERES);
     return RTM_OK;
+}
+
+// ---- binned sphere path: the host's plan (BinArgs, rtm_kernels.h) ----
+// Per tile of BIN_W x BIN_H pixels, how many spheres' pixel ranges reach it: a sphere's
+// tile rectangle follows from its integer ranges (project_sphere's ix0..ix1 x iy0..iy1),
+// a 2-D difference array over the tile grid takes the rectangles in O(n), its prefix sums
+// give the counts in O(tiles).  An empty range (ix0 > ix1) is in no tile.  rtm_bin_plan
+// returns these counts; the render path scans them into offsets, and bin_fill_kernel
+// tests the same ranges against the same tiles, so its lists have exactly these lengths.
+struct BinPlan {
+    int32_t tx = 0, ty = 0;
+    std::vector<int32_t> counts;  // tx * ty, row-major
+    int64_t total = 0;
+};
+
+// bw: the tile width (BIN_W; RTM_MAX_DIM for the fill's first pass, whose "tiles" are
+// whole tile rows)
+void bin_counts(const RasterSphereK* sph, int32_t n, int32_t W, int32_t H, BinPlan& p, int32_t bw = BIN_W) {
+    p.tx = (W + bw - 1) / bw;
+    p.ty = (H + BIN_H - 1) / BIN_H;
+    const size_t pitch = (size_t)p.tx + 1;
+    std::vector<int32_t> d(pitch * ((size_t)p.ty + 1), 0);
+    for (int32_t i = 0; i < n; ++i) {
+        const RasterSphereK& k = sph[i];
+        if (k.ix0 > k.ix1 || k.iy0 > k.iy1) continue;
+        const size_t x0 = (size_t)(k.ix0 / bw), x1 = (size_t)(k.ix1 / bw) + 1;
+        const size_t y0 = (size_t)(k.iy0 / BIN_H), y1 = (size_t)(k.iy1 / BIN_H) + 1;
+        ++d[y0 * pitch + x0];
+        --d[y0 * pitch + x1];
+        --d[y1 * pitch + x0];
+        ++d[y1 * pitch + x1];
+    }
+    p.counts.assign((size_t)p.tx * (size_t)p.ty, 0);
+    p.total = 0;
+    for (size_t y = 0; y < (size_t)p.ty; ++y) {
+        int32_t run = 0;
+        for (size_t x = 0; x < (size_t)p.tx; ++x) {
+            run += d[y * pitch + x];
+            const int32_t c = run + (y ? p.counts[(y - 1) * (size_t)p.tx + x] : 0);
+            p.counts[y * (size_t)p.tx + x] = c;
+            p.total += c;
+        }
+    }
 }
 
 int build_frame(FrameArgs& a, const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow, int32_t W,
@@ -713,6 +777,13 @@ struct rtm_ctx {
     int32_t batch_last = 1;                    // frames per launch of the last frame-sequence call
     int32_t eye_blocks_last = 0;               // the last eye launch ran 8 x 8-pixel blocks (rtm_ctx_last_eye_blocks)
     std::unique_ptr<BatchRing> batch;          // lane 0's batch uploads
+    // binned sphere path (more than RTM_MAX_SPHERES spheres): each frame's tables, offsets
+    // and lists take one slot of this ring, so a frame sequence never overwrites what an
+    // earlier frame still reads
+    std::unique_ptr<BatchRing> bins;
+    int32_t sphere_path_last = 0;                     // rtm_ctx_last_sphere_path
+    const int32_t* bin_written = nullptr;  // the last binned frame's BinArgs::written (device), 2 * bin_tiles
+    int32_t bin_tiles = 0;
     std::vector<TimingSlot> ring;  // per-render kernel events (capacity = ring.size())
     int64_t renders = 0;           // renders recorded into the ring
     int64_t calls = 0;             // renders enqueued (for the stride)
@@ -1108,6 +1179,46 @@ void note_trivial(rtm_ctx* ctx, const ShadowPart& sh) {
     ctx->smap_h = sh.H;
 }
 
+// The binned path's ring of upload slots (BatchRing), created at first use.  (enqueue_batch
+// keeps its own text of this protocol: the batched headline path is left as it was.)
+int ensure_ring(rtm_ctx* ctx, std::unique_ptr<BatchRing>& brp) {
+    if (brp) return RTM_OK;
+    std::unique_ptr<BatchRing> b(new BatchRing);
+    b->device = ctx->device;
+    for (int j = 0; j < BatchRing::R; ++j) {
+        HIP_TRY(hipEventCreateWithFlags(&b->copied[j], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&b->used[j], hipEventDisableTiming));
+    }
+    brp = std::move(b);
+    return RTM_OK;
+}
+
+// The ring's next slot with `up` bytes of pinned staging and `dev_bytes` of device memory.
+int ring_slot(rtm_ctx* ctx, BatchRing& br, size_t up, size_t dev_bytes, int* slot) {
+    const int j = br.next;
+    br.next = (br.next + 1) % BatchRing::R;
+    HIP_TRY(hipEventSynchronize(br.copied[j]));  // the slot's previous upload has left the host buffer
+    if (br.host_bytes[j] < up) {
+        if (br.host[j]) HIP_TRY(hipHostFree(br.host[j]));
+        br.host[j] = nullptr;
+        br.host_bytes[j] = 0;
+        // (pinned as enqueue_batch pins its slots)
+        if (hipHostMalloc(&br.host[j], up, hipHostMallocDefault) != hipSuccess) {
+            br.host[j] = nullptr;
+            return fail(RTM_ERR_OOM, "hipHostMalloc(%zu) failed", up);
+        }
+        br.host_bytes[j] = up;
+        HIP_TRY(hipHostGetDevicePointer(&br.host_dev[j], br.host[j], 0));
+    }
+    if (br.dev[j].bytes < dev_bytes) {
+        HIP_TRY(hipEventSynchronize(br.used[j]));  // no kernel still reads the old device slot
+        int rc = br.dev[j].ensure(dev_bytes, ctx->device);
+        if (rc) return rc;
+    }
+    *slot = j;
+    return RTM_OK;
+}
+
 // lane 0: the context's own stream and buffers; lane k > 0: ctx->lanes[k-1]
 int enqueue_frame(rtm_ctx* ctx, FrameArgs& a, const FrameExtra* x, void* out_dev, StatsK* stats, int lane = 0,
                   int32_t fmt = RTM_FORMAT_RGBA32F) {
@@ -1164,12 +1275,201 @@ int enqueue_frame(rtm_ctx* ctx, FrameArgs& a, const FrameExtra* x, void* out_dev
     if (slot) HIP_TRY(hipEventRecord(slot->ev[2], s));
     if ((rc = launch_eye_pass(a, smap, out_dev, s, stats, tabs))) return fail(rc, "eye pass launch failed");
     ctx->eye_blocks_last = 0;  // (single frames render 64 x 1 rows)
+    ctx->sphere_path_last = 0;
     if (slot) {
         HIP_TRY(hipEventRecord(slot->ev[3], s));
         slot->shadow = !fused;
         ctx->renders++;
     }
     return RTM_OK;
+}
+
+
+// One frame of the binned sphere path (validated by the caller: validate_frame with
+// many_ok): the per-camera sphere tables (project_sphere / shade_sphere, the arithmetic of
+// the kernel-argument path) and the list offsets go through a ring slot's pinned staging
+// into device memory on the context's stream (launch_pull); then bin_fill_kernel, the
+// shadow pass into the context's f64 shadow map, and the eye pass.  One lane, one frame per
+// launch.  RTM_FLAG_FUSED_SHADOW is served by materialising the map: the same image bits.
+int enqueue_binned_frame(rtm_ctx* ctx, const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow,
+                         int32_t W, int32_t H, int32_t steps, int32_t flags, int32_t fmt, int32_t row_begin,
+                         int32_t row_end, void* out_dev);
+
+// (the frame's host tables are std::vectors sized by the scene: no exception crosses the ABI)
+int enqueue_binned(rtm_ctx* ctx, const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow, int32_t W,
+                   int32_t H, int32_t steps, int32_t flags, int32_t fmt, int32_t row_begin, int32_t row_end,
+                   void* out_dev) {
+    try {
+        return enqueue_binned_frame(ctx, scene, eye, shadow, W, H, steps, flags, fmt, row_begin, row_end, out_dev);
+    } catch (const std::bad_alloc&) {
+        return fail(RTM_ERR_OOM, "out of host memory for the tables of %d spheres", scene->n_spheres);
+    }
+}
+
+int enqueue_binned_frame(rtm_ctx* ctx, const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow,
+                         int32_t W, int32_t H, int32_t steps, int32_t flags, int32_t fmt, int32_t row_begin,
+                         int32_t row_end, void* out_dev) {
+    int rc;
+    const int32_t n = scene->n_spheres;
+    hipStream_t s = ctx->stream;
+    ctx->bin_written = nullptr;  // (the slot it points into may be regrown below)
+    BinArgs a;
+    std::memset(&a, 0, sizeof a);
+    ShadowPart& sh = a.sh;
+    for (int i = 0; i < scene->n_patches; ++i) sh.patch[i] = patch_k(scene->patches[i]);
+    sh.cam = cam_k(*shadow);
+    sh.W = W;
+    sh.H = H;
+    sh.n_spheres = 0;  // (sh.sph is unused: the spheres are in the device tables)
+    sh.n_patches = scene->n_patches;
+    sh.steps = steps;
+    sh.flags = flags | RTM_FLAG_NO_SHADOW_RASTER;  // shadow_texel: the march alone
+    sh.cull_x0 = sh.cull_y0 = 1;                   // (an empty union)
+    sh.smap_fmt = SMAP_F64;
+    sh.smap_bw = (int16_t)((W + 127) / 128);
+    if ((rc = ensure_tables(ctx, steps, W, H, shadow, sh.patch, sh.n_patches, &sh.tab))) return rc;
+    a.eye = cam_k(*eye);
+    a.n = n;
+    a.flags = flags;
+    a.row_begin = row_begin;
+    a.row_end = row_end;
+    DevTabs ft{};
+    if ((rc = format_tabs(ctx, fmt, W, out_dev, ft))) return rc;
+    a.enc = ft.enc;
+    a.fmt = ft.fmt;
+    a.bg = ft.bg;
+    // the upload: [eye sph | shadow sph | shade | eye offsets | shadow offsets | eye row offsets | shadow row offsets]
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const int32_t tx = (W + BIN_W - 1) / BIN_W, ty = (H + BIN_H - 1) / BIN_H;
+    const size_t nt = (size_t)tx * (size_t)ty;
+    const size_t o_esph = 0, o_ssph = up(o_esph + sizeof(RasterSphereK) * (size_t)n);
+    const size_t o_shade = up(o_ssph + sizeof(RasterSphereK) * (size_t)n);
+    const size_t o_eoff = up(o_shade + sizeof(ShadeSphereK) * (size_t)n);
+    const size_t o_soff = up(o_eoff + sizeof(int32_t) * (nt + 1));
+    const size_t o_eroff = up(o_soff + sizeof(int32_t) * (nt + 1));
+    const size_t o_sroff = up(o_eroff + sizeof(int32_t) * ((size_t)ty + 1));
+    const size_t up_bytes = up(o_sroff + sizeof(int32_t) * ((size_t)ty + 1));
+    // the tables, built in pageable memory first: the totals size the slot
+    std::vector<RasterSphereK> esph((size_t)n), ssph((size_t)n);
+    auto project = [&](int32_t b, int32_t e) {
+        for (int32_t i = b; i < e; ++i) {
+            esph[(size_t)i] = project_sphere(*eye, scene->spheres[i], W, H);
+            ssph[(size_t)i] = project_sphere(*shadow, scene->spheres[i], W, H);
+        }
+    };
+    // project_sphere's exact pixel ranges are four binary searches per sphere and camera
+    // (0.56 us per sphere measured: 37 ms of host time per frame at 65536 spheres, the
+    // whole frame time); large scenes split the loop over a few threads -- each sphere's
+    // record depends on that sphere alone, so the tables are the same bytes
+    const int nth = n >= 2048 ? std::min<int>(8, n / 1024) : 1;
+    auto part = [&](int k) { return (int32_t)((int64_t)n * k / nth); };
+    std::vector<std::thread> th;
+    th.reserve((size_t)nth);
+    int started = 1;  // parts [0, started) have a thread (part 0: this one)
+    try {
+        for (; started < nth; ++started) th.emplace_back(project, part(started), part(started + 1));
+    } catch (const std::system_error&) {
+        // no more threads to be had: this thread takes the parts that got none
+    }
+    project(part(0), part(1));
+    for (int k = started; k < nth; ++k) project(part(k), part(k + 1));
+    for (auto& t : th) t.join();
+    BinPlan pe, ps, re, rs;  // per tile, and per tile row (the fill's first pass)
+    bin_counts(esph.data(), n, W, H, pe);
+    bin_counts(ssph.data(), n, W, H, ps);
+    bin_counts(esph.data(), n, W, H, re, RTM_MAX_DIM);
+    bin_counts(ssph.data(), n, W, H, rs, RTM_MAX_DIM);
+    if (pe.total > INT32_MAX || ps.total > INT32_MAX || re.total > INT32_MAX || rs.total > INT32_MAX)
+        return fail(RTM_ERR_OOM, "the frame's sphere lists need %lld + %lld entries, past 2^31-1 per viewport",
+                    (long long)std::max(pe.total, re.total), (long long)std::max(ps.total, rs.total));
+    const size_t o_elist = up_bytes, o_slist = up(o_elist + sizeof(int32_t) * (size_t)pe.total);
+    // (device only: the lists, and the per-tile counts the fill kernel reports)
+    const size_t o_wr = up(o_slist + sizeof(int32_t) * (size_t)ps.total);
+    const size_t o_erl = up(o_wr + sizeof(int32_t) * 2 * nt);
+    const size_t o_srl = up(o_erl + sizeof(int32_t) * (size_t)re.total);
+    const size_t dev_bytes = up(o_srl + sizeof(int32_t) * (size_t)rs.total);
+    int j = 0;
+    if ((rc = ensure_ring(ctx, ctx->bins)) || (rc = ring_slot(ctx, *ctx->bins, up_bytes, dev_bytes, &j))) return rc;
+    BatchRing& br = *ctx->bins;
+    char* hb = (char*)br.host[j];
+    char* db = (char*)br.dev[j].p;
+    std::memcpy(hb + o_esph, esph.data(), sizeof(RasterSphereK) * (size_t)n);
+    std::memcpy(hb + o_ssph, ssph.data(), sizeof(RasterSphereK) * (size_t)n);
+    // shade is indexed by id: the reference shades spherePrimitives[id] (main.rs:158, 748),
+    // i.e. the sphere at scene index id, whatever sphere carried that id
+    ShadeSphereK* shade = (ShadeSphereK*)(hb + o_shade);
+    for (int32_t i = 0; i < n; ++i) shade[i] = shade_sphere(scene->spheres[i]);
+    auto scan = [](const BinPlan& p, int32_t* off) {
+        int32_t acc = 0;
+        for (size_t t = 0; t < p.counts.size(); ++t) {
+            off[t] = acc;
+            acc += p.counts[t];
+        }
+        off[p.counts.size()] = acc;
+    };
+    scan(pe, (int32_t*)(hb + o_eoff));
+    scan(ps, (int32_t*)(hb + o_soff));
+    scan(re, (int32_t*)(hb + o_eroff));
+    scan(rs, (int32_t*)(hb + o_sroff));
+    a.eye_sph = (const RasterSphereK*)(db + o_esph);
+    a.sh_sph = (const RasterSphereK*)(db + o_ssph);
+    a.shade = (const ShadeSphereK*)(db + o_shade);
+    a.eye_off = (const int32_t*)(db + o_eoff);
+    a.sh_off = (const int32_t*)(db + o_soff);
+    a.written = (int32_t*)(db + o_wr);
+    a.eye_list = (int32_t*)(db + o_elist);
+    a.sh_list = (int32_t*)(db + o_slist);
+    a.eye_roff = (const int32_t*)(db + o_eroff);
+    a.sh_roff = (const int32_t*)(db + o_sroff);
+    a.eye_rlist = (int32_t*)(db + o_erl);
+    a.sh_rlist = (int32_t*)(db + o_srl);
+    a.eye_rrefs = (int32_t)re.total;
+    a.sh_rrefs = (int32_t)rs.total;
+    a.tiles_x = tx;
+    a.tiles_y = ty;
+    a.n_tiles = (int32_t)nt;
+    a.eye_refs = (int32_t)pe.total;
+    a.sh_refs = (int32_t)ps.total;
+    if ((rc = ctx->smap.ensure((size_t)smap_bytes(SMAP_F64, W, H), ctx->device))) return rc;
+    double* smap = (double*)ctx->smap.p;
+    if ((rc = launch_pull(br.host_dev[j], up_bytes, db, s))) return fail(rc, "sphere table pull failed");
+    HIP_TRY(hipEventRecord(br.copied[j], s));
+    if ((rc = launch_bin_fill(a, s))) return fail(rc, "sphere list fill launch failed");
+    TimingSlot* slot = next_slot(ctx);
+    if (slot) HIP_TRY(hipEventRecord(slot->ev[0], s));
+    if ((rc = launch_bin_shadow(a, smap, s))) return fail(rc, "binned shadow pass launch failed");
+    if (slot) HIP_TRY(hipEventRecord(slot->ev[1], s));
+    ctx->smap_w = W;
+    ctx->smap_h = H;
+    ctx->have_shadow_pass = true;
+    ctx->last_trivial = false;
+    ctx->last_smap = smap;
+    ctx->last_sh = sh;
+    if (slot) HIP_TRY(hipEventRecord(slot->ev[2], s));
+    if ((rc = launch_bin_eye(a, smap, out_dev, s))) return fail(rc, "binned eye pass launch failed");
+    if (slot) {
+        HIP_TRY(hipEventRecord(slot->ev[3], s));
+        slot->shadow = true;
+        ctx->renders++;
+    }
+    HIP_TRY(hipEventRecord(br.used[j], s));
+    ctx->eye_blocks_last = 0;
+    ctx->sphere_path_last = 1;
+    ctx->bin_written = a.written;
+    ctx->bin_tiles = (int32_t)nt;
+    return RTM_OK;
+}
+
+// A frame of more than RTM_MAX_SPHERES spheres for the device-output calls.
+int render_binned(rtm_ctx* ctx, const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow, int32_t W,
+                  int32_t H, int32_t steps, int32_t flags, int32_t fmt, int32_t row_begin, int32_t row_end,
+                  void* out_dev) {
+    int rc;
+    if ((rc = validate_frame(scene, eye, shadow, W, H, steps, flags, true))) return rc;
+    if (row_begin < 0 || row_end > H || row_begin >= row_end)
+        return fail(RTM_ERR_INVALID, "row range [%d,%d) outside [0,%d)", row_begin, row_end, H);
+    DeviceGuard g(ctx->device);
+    return enqueue_binned(ctx, scene, eye, shadow, W, H, steps, flags, fmt, row_begin, row_end, out_dev);
 }
 
 // How many lanes a frame sequence spreads over.  Frames are independent (own
@@ -1459,6 +1759,7 @@ int enqueue_batch(rtm_ctx* ctx, int lane, FrameArgs* fa, const FrameExtra* const
         return fail(rc, "batched eye pass failed");
     if (t0.rtmask) br.mask_buf = new_buf;  // (a batch without masks leaves the lane's words as they were)
     ctx->eye_blocks_last = blocks;
+    ctx->sphere_path_last = 0;
     if (slot) {
         HIP_TRY(hipEventRecord(slot->ev[3], s));
         slot->shadow = !fused;
@@ -1538,6 +1839,7 @@ void rtm_ctx_destroy(rtm_ctx* ctx) {
         }
         ctx->lanes.clear();
         ctx->batch.reset();
+        ctx->bins.reset();
         if (ctx->fork) (void)hipEventDestroy(ctx->fork);
         for (auto& sl : ctx->ring)
             for (auto& e : sl.ev)
@@ -1642,6 +1944,58 @@ int rtm_ctx_last_batch(rtm_ctx* ctx, int32_t* frames) {
 int rtm_ctx_last_eye_blocks(rtm_ctx* ctx, int32_t* blocks) {
     if (!ctx || !blocks) return fail(RTM_ERR_INVALID, "bad arguments");
     *blocks = ctx->eye_blocks_last;
+    return RTM_OK;
+}
+
+int rtm_ctx_last_sphere_path(rtm_ctx* ctx, int32_t* binned) {
+    if (!ctx || !binned) return fail(RTM_ERR_INVALID, "bad arguments");
+    *binned = ctx->sphere_path_last;
+    return RTM_OK;
+}
+
+int rtm_ctx_last_bin_refs(rtm_ctx* ctx, int64_t* eye_refs, int64_t* shadow_refs) {
+    if (!ctx || !eye_refs || !shadow_refs) return fail(RTM_ERR_INVALID, "bad arguments");
+    *eye_refs = *shadow_refs = 0;
+    if (!ctx->bin_written) return RTM_OK;  // no binned frame yet
+    DeviceGuard g(ctx->device);
+    const size_t nt = (size_t)ctx->bin_tiles;
+    std::vector<int32_t> w;
+    try {
+        w.resize(2 * nt);
+    } catch (const std::bad_alloc&) {
+        return fail(RTM_ERR_OOM, "out of host memory for %zu tile counts", 2 * nt);
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(w.data(), ctx->bin_written, sizeof(int32_t) * w.size(), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < nt; ++t) {
+        *eye_refs += w[t];
+        *shadow_refs += w[nt + t];
+    }
+    return RTM_OK;
+}
+
+int rtm_bin_plan(const rtm_scene* scene, const rtm_camera* cam, int32_t width, int32_t height, int32_t* tile_w,
+                 int32_t* tile_h, int32_t* counts, int64_t capacity, int64_t* n_tiles) {
+    if (!tile_w || !tile_h || !n_tiles) return fail(RTM_ERR_INVALID, "tile_w/tile_h/n_tiles is NULL");
+    int rc;
+    if ((rc = validate_scene(scene, true)) || (rc = validate_camera(cam, "bin")) || (rc = validate_dims(width, height)))
+        return rc;
+    if (cam->type != RTM_CAMERA_ORTHOGONAL) return fail(RTM_ERR_UNSUPPORTED, "the binner needs an ORTHOGONAL camera");
+    *tile_w = BIN_W;
+    *tile_h = BIN_H;
+    *n_tiles = (int64_t)((width + BIN_W - 1) / BIN_W) * ((height + BIN_H - 1) / BIN_H);
+    if (capacity < *n_tiles) return RTM_OK;  // the caller sizes `counts` and calls again
+    if (!counts) return fail(RTM_ERR_INVALID, "counts is NULL");
+    try {
+        std::vector<RasterSphereK> sph((size_t)scene->n_spheres);
+        for (int32_t i = 0; i < scene->n_spheres; ++i)
+            sph[(size_t)i] = project_sphere(*cam, scene->spheres[i], width, height);
+        BinPlan p;
+        bin_counts(sph.data(), scene->n_spheres, width, height, p);
+        std::memcpy(counts, p.counts.data(), sizeof(int32_t) * p.counts.size());
+    } catch (const std::bad_alloc&) {
+        return fail(RTM_ERR_OOM, "out of host memory for the plan of %d spheres", scene->n_spheres);
+    }
     return RTM_OK;
 }
 
@@ -1773,6 +2127,30 @@ int rtm_render_frames_async(rtm_ctx* ctx, int32_t n_frames, const rtm_scene* sce
     // vs 79.1 us/frame, profiles/r01_ab_pipe.txt; a lane stagger lost at 3840x2160 and
     // 512x512, profiles/r02_ab_batch.txt.  Both are gone.)
     DeviceGuard g(ctx->device);
+    bool any_many = false;
+    for (int32_t i = 0; i < n_frames; ++i) any_many = any_many || scenes[i].n_spheres > RTM_MAX_SPHERES;
+    if (any_many) {
+        // a sequence with a scene of more than RTM_MAX_SPHERES spheres: one frame per launch
+        // on the context's own stream, each frame on its own sphere path
+        ctx->lanes_last = 1;
+        ctx->batch_last = 1;
+        FrameArgs a;
+        FrameExtra x;
+        for (int32_t i = 0; i < n_frames; ++i) {
+            int rc;
+            if (many_spheres(&scenes[i])) {
+                if ((rc = validate_frame(&scenes[i], eye, shadow, width, height, march_steps, flags, true))) return rc;
+                rc = enqueue_binned(ctx, &scenes[i], eye, shadow, width, height, march_steps, flags, RTM_FORMAT_RGBA32F,
+                                    0, height, out_rgba_dev[i]);
+            } else {
+                if ((rc = build_frame(a, &scenes[i], eye, shadow, width, height, march_steps, flags))) return rc;
+                build_extra(&scenes[i], eye, width, height, x);
+                rc = enqueue_frame(ctx, a, &x, out_rgba_dev[i], nullptr, 0);
+            }
+            if (rc) return rc;
+        }
+        return RTM_OK;
+    }
     int B = std::min<int32_t>(frame_batch(ctx->batch_req, width, height), n_frames);
     int L = frame_lanes(ctx->lanes_req, n_frames, width, height, out_rgba_dev, B);
     int rc = RTM_OK;
@@ -1865,6 +2243,9 @@ int rtm_render_rows_async(rtm_ctx* ctx, const rtm_scene* scene, const rtm_camera
     if (!out_dev) return fail(RTM_ERR_INVALID, "out_dev is NULL");
     int rc = validate_format(format, out_dev);
     if (rc) return rc;
+    if (many_spheres(scene))
+        return render_binned(ctx, scene, eye, shadow, width, height, march_steps, flags, format, row_begin, row_end,
+                             out_dev);
     FrameArgs a;
     if ((rc = build_frame(a, scene, eye, shadow, width, height, march_steps, flags))) return rc;
     if (row_begin < 0 || row_end > height || row_begin >= row_end)
@@ -1881,17 +2262,22 @@ int rtm_render_ex(const rtm_scene* scene, const rtm_camera* eye, const rtm_camer
                   int32_t height, int32_t march_steps, int32_t flags, int32_t format, void* out_host) {
     if (!out_host) return fail(RTM_ERR_INVALID, "out is NULL");
     if (!format_bytes(format)) return fail(RTM_ERR_INVALID, "unknown output format %d", format);
+    const bool many = many_spheres(scene);
     FrameArgs a;
-    int rc = build_frame(a, scene, eye, shadow, width, height, march_steps, flags);
+    int rc = many ? validate_frame(scene, eye, shadow, width, height, march_steps, flags, true)
+                  : build_frame(a, scene, eye, shadow, width, height, march_steps, flags);
     if (rc) return rc;
     rtm_ctx* ctx = default_ctx(&rc);
     if (!ctx) return rc;
     FrameExtra x;
-    build_extra(scene, eye, width, height, x);
+    if (!many) build_extra(scene, eye, width, height, x);
     DeviceGuard g(ctx->device);
     const size_t bytes = (size_t)format_bytes(format) * (size_t)width * (size_t)height;
     if ((rc = ctx->out.ensure(bytes, ctx->device))) return rc;
-    if ((rc = enqueue_frame(ctx, a, &x, ctx->out.p, nullptr, 0, format))) return rc;
+    if ((rc = many ? enqueue_binned(ctx, scene, eye, shadow, width, height, march_steps, flags, format, 0, height,
+                                    ctx->out.p)
+                   : enqueue_frame(ctx, a, &x, ctx->out.p, nullptr, 0, format)))
+        return rc;
     HIP_TRY(hipMemcpyAsync(out_host, ctx->out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return RTM_OK;
@@ -1899,6 +2285,14 @@ int rtm_render_ex(const rtm_scene* scene, const rtm_camera* eye, const rtm_camer
 
 int rtm_render(const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow, int32_t width,
                int32_t height, int32_t march_steps, int32_t flags, float* out_rgba) {
+    // The ABI v1 call keeps its v1 answer to a 17th sphere: existing callers (and
+    // tests/test_gpu_parity.py::test_error_codes) rely on RTM_ERR_INVALID here.  Its superset
+    // rtm_render_ex renders such a scene into host memory.
+    if (many_spheres(scene))
+        return fail(RTM_ERR_INVALID,
+                    "n_spheres=%d outside [0,%d] for rtm_render (up to %d spheres render through rtm_render_ex, "
+                    "rtm_render_async, rtm_render_rows_async and rtm_render_frames_async)",
+                    scene->n_spheres, RTM_MAX_SPHERES, RTM_MAX_SCENE_SPHERES);
     return rtm_render_ex(scene, eye, shadow, width, height, march_steps, flags, RTM_FORMAT_RGBA32F, out_rgba);
 }
 

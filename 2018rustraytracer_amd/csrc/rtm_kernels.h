@@ -416,4 +416,47 @@ int launch_fill(double* p, int64_t n, double v, int32_t* ip, int32_t iv, void* s
 // cleared; blocking on `stream`.
 int read_oob_reads(unsigned long long* count, void* stream);
 
+// ---- binned sphere path: scenes of RTM_MAX_SPHERES + 1 .. RTM_MAX_SCENE_SPHERES spheres ----
+// The sphere tables live in device memory (sized from the scene, not a cap), and a
+// per-tile list of candidate spheres in ascending scene index drives the passes.  A tile
+// is BIN_W x BIN_H pixels (a bin wave's 64 x 1 row lies inside one tile); both viewports
+// have the image's size, so they share the tile grid.  The host plans the lists exactly
+// (rtm_api.cpp bin_counts: the spheres' pixel ranges, a 2-D difference array, a scan), so
+// offsets and the total are known before any launch; bin_fill_kernel writes the entries.
+// The fill runs in two passes so that no tile walks the whole scene: first one list per
+// tile ROW (a "tile" as wide as the image, planned by the same code), then each tile
+// filters its row's list.  Both keep ascending scene index.
+constexpr int BIN_W = 64, BIN_H = 8;
+struct BinArgs {
+    ShadowPart sh;                 // patches, shadow camera, march tables, dims, steps; sh.sph is unused
+                                   // (n_spheres = 0) and sh.flags carries RTM_FLAG_NO_SHADOW_RASTER:
+                                   // shadow_texel then runs the march alone
+    CamK eye;
+    const RasterSphereK* eye_sph;  // n, eye camera projection, by scene index
+    const RasterSphereK* sh_sph;   // n, shadow camera projection, by scene index
+    const ShadeSphereK* shade;     // n, by id
+    const int32_t* eye_off;        // n_tiles + 1 list offsets (row-major tiles)
+    const int32_t* sh_off;
+    int32_t* eye_list;             // eye_refs sphere indices
+    int32_t* sh_list;              // sh_refs
+    const int32_t* eye_roff;       // tiles_y + 1 offsets of the tile rows' lists
+    const int32_t* sh_roff;
+    int32_t* eye_rlist;            // eye_rrefs sphere indices
+    int32_t* sh_rlist;             // sh_rrefs
+    int32_t* written;              // 2 * n_tiles: entries bin_fill_kernel wrote per tile (eye tiles, then shadow)
+    const void* enc;               // DevTabs::enc
+    int32_t n, tiles_x, tiles_y, n_tiles;
+    int32_t eye_refs, sh_refs;
+    int32_t eye_rrefs, sh_rrefs;
+    int32_t row_begin, row_end;    // eye rows of the launch (the output's row 0 = row_begin)
+    int32_t flags;                 // the frame's RTM_FLAG_*
+    int32_t fmt;                   // DevTabs::fmt
+    uint32_t bg;                   // DevTabs::bg
+    int32_t pad;
+};
+static_assert(sizeof(BinArgs) <= 2048, "BinArgs stays well below the 4 KiB kernarg segment");
+int launch_bin_fill(const BinArgs& a, void* stream);
+int launch_bin_shadow(const BinArgs& a, double* smap, void* stream);
+int launch_bin_eye(const BinArgs& a, const double* smap, void* out, void* stream);
+
 }  // namespace rtm

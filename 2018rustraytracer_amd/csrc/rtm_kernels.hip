@@ -2067,6 +2067,56 @@ __device__ __forceinline__ const T* const_table(const T* p) {
     return (const T*)(const __attribute__((address_space(4))) T*)p;
 }
 
+// renderColorImage's pieces as the binned eye pass (bin_eye_tile) uses them: eye_tile's
+// operations in eye_tile's order, so the same bits on either sphere path.  (eye_tile keeps
+// its own text: calling these from it took the single-frame eye kernel from 62 to 68 VGPRs
+// and from 8 to 7 waves per SIMD, DESIGN.md "Many spheres".)
+// World position, normal and colour of a sphere hit (main.rs:729-759): s is the shading
+// record of the hit's id, bz / bh the projected depth and height of the rasterized sphere.
+__device__ __forceinline__ void sphere_surface(const ShadeSphereK& s, double bz, double bh, const double o[3],
+                                               const double d[3], double w[3], double n[3], double col[3]) {
+    const double depth = bz - bh * s.r;  // calcDepth (main.rs:160-162)
+    w[0] = o[0] + d[0] * depth;
+    w[1] = o[1] + d[1] * depth;
+    w[2] = o[2] + d[2] * depth;
+    n[0] = (w[0] - s.px) * s.inv_r;
+    n[1] = (w[1] - s.py) * s.inv_r;
+    n[2] = (w[2] - s.pz) * s.inv_r;
+    col[0] = s.cr;
+    col[1] = s.cg;
+    col[2] = s.cb;
+}
+
+// diffuse + specular of normal n seen from direction v (main.rs:810-834)
+__device__ __forceinline__ double light_terms(double nx, double ny, double nz, double vx, double vy, double vz) {
+    // light (1,0,0).scale(-1.0) (main.rs:810-813)
+    const double Lx = 1.0 * -1.0, Ly = 0.0 * -1.0, Lz = 0.0 * -1.0;
+    const double diffuse = fmax(nx * Lx + ny * Ly + nz * Lz, 0.0);
+    // reflect(L, n) = L - n*(-2 dot(L,n))  (main.rs:2872-2875, sign as written)
+    const double k2 = -2.0 * (Lx * nx + Ly * ny + Lz * nz);
+    const double Rx = Lx - nx * k2, Ry = Ly - ny * k2, Rz = Lz - nz * k2;
+    double sp = fmax(vx * Rx + vy * Ry + vz * Rz, 0.0);
+    sp = sp * sp;  // powi(32): five squarings (compiler-rt __powidf2)
+    sp = sp * sp;
+    sp = sp * sp;
+    sp = sp * sp;
+    sp = sp * sp;
+    return diffuse + sp;
+}
+
+// shadow mapping's projection of world point w (main.rs:836-856): texel (tx, ty) of a
+// Ws x Hs map and the depth qz it is compared with
+__device__ __forceinline__ void shadow_lookup_coords(const CamK& shadow, int Ws, int Hs, double wx, double wy,
+                                                     double wz, int64_t& tx, int64_t& ty, double& qz) {
+    const double dfx = wx - shadow.pos[0], dfy = wy - shadow.pos[1], dfz = wz - shadow.pos[2];
+    const double qx = dfx * shadow.side[0] + dfy * shadow.side[1] + dfz * shadow.side[2];
+    const double qy = dfx * shadow.up[0] + dfy * shadow.up[1] + dfz * shadow.up[2];
+    qz = dfx * shadow.dir[0] + dfy * shadow.dir[1] + dfz * shadow.dir[2];
+    const int64_t hw = Ws / 2, hh = Hs / 2;
+    tx = tex_index(hw, qx * (double)hw);
+    ty = tex_index(hh, qy * (double)hh);
+}
+
 // BLK: the waves are 8 x 8 pixel blocks (workgroup bx: 4 blocks side by side, block row
 // by: 8 rows), for the batched RT 3 frames without shadows and without stripes: a compact
 // primitive touches fewer blocks than 64 x 1 rows, and a block's cone is narrower.
@@ -2772,6 +2822,226 @@ __global__ void fill_kernel(double* __restrict__ p, int64_t n, double v, int32_t
     }
 }
 
+// ---- binned sphere path (BinArgs, rtm_kernels.h) ----
+
+// One wave per (tile, viewport): the wave walks its candidates in chunks of 64, lane l
+// tests candidate base + l's pixel ranges against the tile, and a ballot + prefix popcount
+// compact the survivors into the tile's slice at the host-computed offset -- ascending
+// scene index, no atomics on the list, the same lists for the same frame.  The host
+// planned the slice's length from the same ranges (rtm_api.cpp bin_counts): a count that
+// differs is never written past the slice, and the tile is counted as an out-of-range read.
+// ROWS: the "tile" is a whole tile row and the candidates are all n spheres; else the
+// candidates are the tile's row list (written by the ROWS launch before this one), so a
+// tile walks the spheres that reach its rows, not the scene.
+template <bool ROWS>
+__global__ __launch_bounds__(64) void bin_fill_kernel(const BinArgs a) {
+    const int t = (int)blockIdx.x;  // (t < tiles_y / n_tiles: the grid is that wide)
+    const bool shadow = blockIdx.y != 0;
+    const RasterSphereK* __restrict__ sph = shadow ? a.sh_sph : a.eye_sph;
+    const int32_t* roff = const_table(shadow ? a.sh_roff : a.eye_roff);
+    const int32_t* off = ROWS ? roff : const_table(shadow ? a.sh_off : a.eye_off);
+    const int32_t* rlist = shadow ? a.sh_rlist : a.eye_rlist;  // (ROWS: unread, it is `list`)
+    int32_t* list = ROWS ? (shadow ? a.sh_rlist : a.eye_rlist) : (shadow ? a.sh_list : a.eye_list);
+    const int rrefs = shadow ? a.sh_rrefs : a.eye_rrefs;
+    const int refs = ROWS ? rrefs : (shadow ? a.sh_refs : a.eye_refs);
+    const int o0 = off[t], o1 = off[t + 1];
+    bool bad = o0 < 0 || o1 < o0 || o1 > refs;
+    const int cap = bad ? 0 : o1 - o0;
+    const int row = ROWS ? t : t / a.tiles_x;
+    const int xb = ROWS ? 0 : (t % a.tiles_x) * BIN_W, xe = ROWS ? INT32_MAX : xb + BIN_W - 1;
+    const int ya = row * BIN_H, ye = ya + BIN_H - 1;
+    // the candidates: every sphere, or the slice [r0, r1) of the row's list
+    int r0 = 0, r1 = a.n;
+    if (!ROWS) {
+        r0 = roff[row];
+        r1 = roff[row + 1];
+        if (r0 < 0 || r1 < r0 || r1 > rrefs) {
+            bad = true;
+            r0 = r1 = 0;
+        }
+    }
+    const int l = (int)threadIdx.x;
+    int cnt = 0;
+    for (int base = r0; base < r1; base += 64) {
+        const int k = base + l;
+        bool m = false;
+        const int i = k < r1 ? (ROWS ? k : rlist[k]) : -1;
+        if ((unsigned)i < (unsigned)a.n) {  // (a row entry is checked like every other index)
+            const RasterSphereK& s = sph[i];
+            // (an empty range, ix0 > ix1, is in no tile: (1, 0) would otherwise "meet" tile 0)
+            m = (s.ix0 <= s.ix1) & (s.iy0 <= s.iy1) & (ye >= s.iy0) & (ya <= s.iy1) & (xe >= s.ix0) & (xb <= s.ix1);
+        }
+        const unsigned long long b = __ballot(m);
+        const int pos = cnt + __popcll(b & ((1ull << l) - 1ull));
+        if (m && pos < cap) list[o0 + pos] = i;
+        cnt += __popcll(b);
+    }
+    if (l == 0) {
+        // (a plain store per tile, summed by rtm_ctx_last_bin_refs: one counter per viewport
+        // had every wave's atomic serialise on one address, 0.4 ms per 3840x2160 frame)
+        if (!ROWS) a.written[(shadow ? a.n_tiles : 0) + t] = min(cnt, cap);
+        if (bad || cnt != cap) atomicAdd(&g_oob_reads, 1ull);
+    }
+}
+
+// The z-test of one pixel over its tile's list (rasterizeSphere in scene order, strict '<'
+// against +INF, main.rs:318: the list ascends, so ties keep the first sphere and a NaN
+// depth never wins).  Wave-uniform tile: the offsets, the list entries and the sphere
+// records are read through the constant address space (scalar loads); every index is
+// checked against its table's length and a bad one is skipped and reported through oob
+// (counted by the caller after its last table load, see eye_tile).
+template <bool BACK>
+__device__ __forceinline__ void bin_raster(const BinArgs& a, const RasterSphereK* sph_, const int32_t* off_,
+                                           const int32_t* list_, int refs, int xb, int yi, bool live, double x,
+                                           double y, double& best, double& bh, double& bz, int& bid, bool& oob) {
+    const RasterSphereK* __restrict__ sph = const_table(sph_);
+    const int32_t* __restrict__ off = const_table(off_);
+    const int32_t* __restrict__ list = const_table(list_);
+    const int tile = (yi / BIN_H) * a.tiles_x + xb / BIN_W;
+    int o0 = 0, o1 = 0;
+    if (tile >= 0 && tile < a.n_tiles) {
+        o0 = off[tile];
+        o1 = off[tile + 1];
+    } else {
+        oob = true;
+    }
+    if (o0 < 0 || o1 < o0 || o1 > refs) {
+        oob = true;
+        o0 = o1 = 0;
+    }
+    for (int e = o0; e < o1; ++e) {
+        const int i = list[e];
+        if ((unsigned)i >= (unsigned)a.n) {
+            oob = true;
+            continue;
+        }
+        const RasterSphereK& s = sph[i];
+        if (!may_cover(s, xb, xb + TILE_X - 1, yi)) continue;  // (the tile has BIN_H rows, the wave one)
+        double h;
+        if (live && cover(s, x, y, h)) {
+            const double depth = BACK ? s.z + h * s.r : s.z - h * s.r;  // EnumFace (main.rs:239, 243)
+            if (depth < best) {
+                best = depth;
+                bh = h;
+                bz = s.z;
+                bid = s.id;
+            }
+        }
+    }
+}
+
+// Shadow viewport of a binned frame: rasterize BACK faces over the texel's tile list, then
+// processRaymarchingRays through shadow_texel with its raster part off (a.sh carries
+// RTM_FLAG_NO_SHADOW_RASTER): the same tables, march_axis and march as every other frame.
+// 64 x 1 texels per wave, f64 map.
+__global__ __launch_bounds__(BLOCK) void bin_shadow_kernel(const BinArgs a, double* __restrict__ smap) {
+    const int xb = (int)blockIdx.x * TILE_X;
+    const int xi = xb + (int)(threadIdx.x & (TILE_X - 1));
+    const int yi = __builtin_amdgcn_readfirstlane((int)blockIdx.y * TILE_Y + (int)(threadIdx.x >> 6));
+    if (yi >= a.sh.H) return;  // (wave-uniform)
+    const bool live = xi < a.sh.W;
+    bool oob = false;
+    double zb = INFINITY, bh = 0.0, bz = 0.0;
+    int bid = -1;
+    if (!(a.flags & RTM_FLAG_NO_SHADOW_RASTER)) {
+        const double x = live ? a.sh.tab.nx[xi] : 0.0;
+        const double y = a.sh.tab.ny[yi];
+        bin_raster<true>(a, a.sh_sph, a.sh_off, a.sh_list, a.sh_refs, xb, yi, live, x, y, zb, bh, bz, bid, oob);
+    }
+    if (live) {
+        ShadowCounts c;
+        const double m = shadow_texel<false>(a.sh, xi, yi, xb, xb + TILE_X - 1, yi, c);  // the march alone
+        if (m < zb) zb = m;  // strict min (main.rs:559)
+        smap[(int64_t)yi * a.sh.W + xi] = zb;
+    }
+    if (__builtin_expect(oob, 0)) note_oob();
+}
+
+// Eye viewport + renderColorImage of a binned frame: eye_tile's wave shape (64 x 1 pixels,
+// 4 waves per workgroup), NDC tables, shading, shadow lookup and frame store, with the
+// wave's tile list in place of the kernel-argument sphere mask.
+template <int FMT>
+__device__ __forceinline__ void bin_eye_tile(const BinArgs& a, const double* __restrict__ smap, void* __restrict__ out) {
+    const int W = a.sh.W, H = a.sh.H;  // (both viewports have the image's size)
+    const int ln = (int)(threadIdx.x & (TILE_X - 1));
+    const int xb = (int)blockIdx.x * TILE_X;
+    const int xi = xb + ln;
+    const int yl = __builtin_amdgcn_readfirstlane((int)blockIdx.y * TILE_Y + (int)(threadIdx.x >> 6));
+    const int yi = a.row_begin + yl;
+    if (yi >= a.row_end || yi >= H) return;  // (wave-uniform)
+    const bool live = xi < W;
+    bool oob = false;
+    float4 c = make_float4(0.0f, 0.2f, 0.2f, 1.0f);  // (0.0, 0.2, 0.2) as f32 (main.rs:718-720)
+    bool shaded = false;
+    const double x = live ? a.sh.tab.nx[xi] : 0.0;
+    const double y = a.sh.tab.ny[yi];
+    double best = INFINITY, bh = 0.0, bz = 0.0;
+    int bid = -1;
+    bin_raster<false>(a, a.eye_sph, a.eye_off, a.eye_list, a.eye_refs, xb, yi, live, x, y, best, bh, bz, bid, oob);
+    if (best < INFINITY) {  // a hit: some depth won the strict '<' against +INF (live lanes only)
+        // the reference shades spherePrimitives[id] (main.rs:158, 748); the host validated
+        // the id (validate_scene), a bad one is counted and clamped into the table
+        const int sid = min(max(bid, 0), a.n - 1);
+        if (sid != bid) oob = true;
+        shaded = true;
+        double o[3], d[3], w[3], n[3], col[3];
+        cam_ray(a.eye, x, y, o, d);
+        sphere_surface(a.shade[sid], bz, bh, o, d, w, n, col);
+        // retViewDirOfPixel, ORTHOGONAL (main.rs:1981-2013)
+        const double base = light_terms(n[0], n[1], n[2], a.eye.dir[0] * -1.0, a.eye.dir[1] * -1.0, a.eye.dir[2] * -1.0);
+        int64_t tx, ty;
+        double qz;
+        shadow_lookup_coords(a.sh.cam, W, H, w[0], w[1], w[2], tx, ty, qz);
+        double dsm = INFINITY;
+        if (ty >= 0 && ty < H && tx >= 0 && tx < W) dsm = smap[ty * W + tx];
+        const bool lit = dsm > qz - 0.0;
+        const double lm = lit ? 1.0 : 0.25;
+        c.x = (float)((base * lm) * col[0]);
+        c.y = (float)((base * lm) * col[1]);
+        c.z = (float)((base * lm) * col[2]);
+    }
+    // the frame store, as eye_tile's: RGBA f32, or writeColorImage's bytes
+    if (FMT == RTM_FORMAT_RGBA32F) {
+        float4* o = reinterpret_cast<float4*>(out);
+        if (live)
+            __builtin_nontemporal_store(f32x4{c.x, c.y, c.z, c.w}, reinterpret_cast<f32x4*>(&o[(int64_t)yl * W + xi]));
+    } else {
+        uint32_t e = a.bg;
+        if (shaded) {
+            const float* T = reinterpret_cast<const float*>(a.enc);
+            const uint8_t* B = reinterpret_cast<const uint8_t*>(a.enc) + 1024;
+            e = enc_byte(c.x, T, B) | (enc_byte(c.y, T, B) << 8) | (enc_byte(c.z, T, B) << 16);
+        }
+        if (FMT == RTM_FORMAT_RGBA8) {
+            uint32_t* o = reinterpret_cast<uint32_t*>(out);
+            if (live) __builtin_nontemporal_store(e | 0xFF000000u, &o[(int64_t)yl * W + xi]);
+        } else {
+            uint8_t* row = reinterpret_cast<uint8_t*>(out) + (int64_t)yl * W * 3;
+            if (a.fmt & FMT_RGB8_DWORDS) {  // (see eye_tile: the wave's 192 bytes as 48 dwords)
+                const int L = min((4 * ln) / 3, TILE_X - 1);
+                const int o = min(4 * ln - 3 * L, 2);
+                const uint32_t p0 = (uint32_t)__shfl((int)e, L);
+                const uint32_t p1 = (uint32_t)__shfl((int)e, min(L + 1, TILE_X - 1));
+                const uint32_t wd = (p0 >> (8 * o)) | (p1 << (8 * (3 - o)));
+                const int nv = min(TILE_X, W - xb);
+                if (ln < (3 * nv) >> 2)
+                    __builtin_nontemporal_store(wd, reinterpret_cast<uint32_t*>(row + 3 * (int64_t)xb) + ln);
+            } else if (live) {
+                row[3 * (int64_t)xi + 0] = (uint8_t)e;
+                row[3 * (int64_t)xi + 1] = (uint8_t)(e >> 8);
+                row[3 * (int64_t)xi + 2] = (uint8_t)(e >> 16);
+            }
+        }
+    }
+    if (__builtin_expect(oob, 0)) note_oob();  // (after the tile's last load, see eye_tile)
+}
+
+template <int FMT>
+__global__ __launch_bounds__(BLOCK) void bin_eye_kernel(const BinArgs a, const double* __restrict__ smap,
+                                                        void* __restrict__ out) {
+    bin_eye_tile<FMT>(a, smap, out);
+}
+
 }  // namespace
 
 namespace {
@@ -3163,6 +3433,28 @@ int launch_fill(double* p, int64_t n, double v, int32_t* ip, int32_t iv, void* s
     int64_t blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, n, v, ip, iv);
+    return launched();
+}
+
+int launch_bin_fill(const BinArgs& a, void* stream) {
+    hipLaunchKernelGGL(bin_fill_kernel<true>, dim3((unsigned)a.tiles_y, 2u), dim3(64), 0, (hipStream_t)stream, a);
+    if (launched()) return RTM_ERR_HIP;
+    hipLaunchKernelGGL(bin_fill_kernel<false>, dim3((unsigned)a.n_tiles, 2u), dim3(64), 0, (hipStream_t)stream, a);
+    return launched();
+}
+
+int launch_bin_shadow(const BinArgs& a, double* smap, void* stream) {
+    hipLaunchKernelGGL(bin_shadow_kernel, grid_for(a.sh.W, a.sh.H), dim3(BLOCK), 0, (hipStream_t)stream, a, smap);
+    return launched();
+}
+
+int launch_bin_eye(const BinArgs& a, const double* smap, void* out, void* stream) {
+    const dim3 g = grid_for(a.sh.W, a.row_end - a.row_begin);
+    const hipStream_t s = (hipStream_t)stream;
+    const int fmt = a.fmt & FMT_MASK;
+    if (fmt == RTM_FORMAT_RGBA8) hipLaunchKernelGGL(bin_eye_kernel<RTM_FORMAT_RGBA8>, g, dim3(BLOCK), 0, s, a, smap, out);
+    else if (fmt == RTM_FORMAT_RGB8) hipLaunchKernelGGL(bin_eye_kernel<RTM_FORMAT_RGB8>, g, dim3(BLOCK), 0, s, a, smap, out);
+    else hipLaunchKernelGGL(bin_eye_kernel<RTM_FORMAT_RGBA32F>, g, dim3(BLOCK), 0, s, a, smap, out);
     return launched();
 }
 

@@ -94,6 +94,22 @@ class Context:
         abi.check(lib, lib.rtm_ctx_last_eye_blocks(self._h, C.byref(n)), "rtm_ctx_last_eye_blocks")
         return bool(n.value)
 
+    def last_sphere_path(self) -> int:
+        """rtm_ctx_last_sphere_path: 0 = the last frame took the kernel-argument sphere path
+        (at most RTM_MAX_SPHERES spheres), 1 = the binned path (device tables and tile lists)."""
+        n = C.c_int32()
+        lib = _lib()
+        abi.check(lib, lib.rtm_ctx_last_sphere_path(self._h, C.byref(n)), "rtm_ctx_last_sphere_path")
+        return int(n.value)
+
+    def last_bin_refs(self):
+        """rtm_ctx_last_bin_refs: (eye, shadow) list entries the device binner wrote for the
+        last binned frame (blocking)."""
+        e, s = C.c_int64(), C.c_int64()
+        lib = _lib()
+        abi.check(lib, lib.rtm_ctx_last_bin_refs(self._h, C.byref(e), C.byref(s)), "rtm_ctx_last_bin_refs")
+        return int(e.value), int(s.value)
+
     def frames_plan(self, width: int, rows: int, n_frames: int):
         """rtm_ctx_frames_plan: (lanes, frames per launch) render_frames_async picks for
         n_frames frames of width x rows with distinct outputs on this context."""
@@ -235,6 +251,24 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+def bin_plan(scene: Scene, cam: Camera, width: int, height: int):
+    """rtm_bin_plan: ((tile_w, tile_h), counts) -- the binned sphere path's tile shape and,
+    as an int32 array of shape (tiles_y, tiles_x), how many spheres the render puts in each
+    tile's list for this camera.  Host only: no context, no device."""
+    sc, keep = scene.to_c()
+    c = cam.to_c()
+    lib = _lib()
+    tw, th, nt = C.c_int32(), C.c_int32(), C.c_int64()
+    abi.check(lib, lib.rtm_bin_plan(C.byref(sc), C.byref(c), width, height, C.byref(tw), C.byref(th), None, 0,
+                                    C.byref(nt)), "rtm_bin_plan")
+    counts = np.zeros(int(nt.value), np.int32)
+    abi.check(lib, lib.rtm_bin_plan(C.byref(sc), C.byref(c), width, height, C.byref(tw), C.byref(th),
+                                    counts.ctypes.data_as(C.POINTER(C.c_int32)), counts.size, C.byref(nt)),
+              "rtm_bin_plan")
+    tiles_x = -(-width // int(tw.value))
+    return (int(tw.value), int(th.value)), counts.reshape(-1, tiles_x)
 
 
 def render_frame(scene: Scene, eye: Camera, shadow: Camera, width: int, height: int, steps: int,

@@ -231,6 +231,37 @@ def scene_b() -> Scene:
     return Scene(spheres, [BENCH_PATCH, SCENE_B_PATCH2])
 
 
+def splitmix64(seed: int):
+    """Generator of splitmix64's uniform doubles u = (next >> 11) / 2**53 in [0, 1)."""
+    mask = (1 << 64) - 1
+    state = seed & mask
+    while True:
+        state = (state + 0x9E3779B97F4A7C15) & mask
+        z = state
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
+        z ^= z >> 31
+        yield (z >> 11) / 2.0 ** 53
+
+
+def sphere_field(n: int, seed: int = 0x2018, rmin: float = 0.01, rmax: float = 0.08,
+                 patches=(BENCH_PATCH,)) -> Scene:
+    """n spheres scattered by splitmix64 (per sphere, in this order: x = -0.6 + 1.2u,
+    y = -0.9 + 1.8u, z = 0.1 + 1.6u, r = rmin + (rmax - rmin)u), colour _COLORS_B[i % 4],
+    id = i: the scenes of the binned sphere path (more than RTM_MAX_SPHERES spheres).
+    With eye_camera() the screen x is the world z, so part of the field lies off-screen
+    and across the right edge."""
+    u = splitmix64(seed)
+    spheres = []
+    for i in range(n):
+        x = -0.6 + 1.2 * next(u)
+        y = -0.9 + 1.8 * next(u)
+        z = 0.1 + 1.6 * next(u)
+        r = rmin + (rmax - rmin) * next(u)
+        spheres.append(PrimitiveSphere(i, Shading(*_COLORS_B[i % 4]), (x, y, z), r))
+    return Scene(spheres, list(patches))
+
+
 def overlapping_spheres() -> Scene:
     """testscene_overlappingSpheres (main.rs:1322-1458): two spheres, shadow pass
     commented out (render with RTM_FLAG_NO_MARCH | RTM_FLAG_NO_SHADOW_RASTER)."""

@@ -41,10 +41,21 @@
 extern "C" {
 #endif
 
-#define RTM_ABI_VERSION 11
+#define RTM_ABI_VERSION 12
 
-/* ---- limits: scene constants travel as kernel arguments (SGPR path) ---- */
+/* ---- limits ----
+ * Up to RTM_MAX_SPHERES spheres, a frame's scene constants travel as kernel arguments
+ * (SGPR path); every call takes such a scene.  ABI v12: a scene of RTM_MAX_SPHERES + 1 ..
+ * RTM_MAX_SCENE_SPHERES spheres (the reference's Vec<PrimitiveSphere> has no bound,
+ * main.rs:404-410) renders on the binned sphere path -- sphere tables in device memory,
+ * per-tile lists of candidate spheres in scene order -- through rtm_render_ex,
+ * rtm_render_async, rtm_render_rows_async and rtm_render_frames_async, with ORTHOGONAL
+ * cameras, patches, and no circle planes, capped cylinders or SDFs; every other call and
+ * combination answers such a scene with RTM_ERR_UNSUPPORTED.  The blocking host-output
+ * form is rtm_render_ex; rtm_render, the ABI v1 call, keeps the answer its callers know,
+ * RTM_ERR_INVALID.  RTM_MAX_SPHERES still sizes rtm_stats::eye_hits. */
 #define RTM_MAX_SPHERES 16
+#define RTM_MAX_SCENE_SPHERES 65536
 #define RTM_MAX_PATCHES 4
 #define RTM_MAX_CIRCLE_PLANES 16
 #define RTM_MAX_CAPPED_CYLINDERS 16
@@ -54,7 +65,8 @@ extern "C" {
 /* ---- status codes ---- */
 #define RTM_OK 0
 #define RTM_ERR_INVALID -1     /* bad argument (null, size, id out of range, ...) */
-#define RTM_ERR_UNSUPPORTED -2 /* valid in the reference but not on this path (a non-orthographic shadow camera) */
+#define RTM_ERR_UNSUPPORTED -2 /* valid in the reference but not on this path (a non-orthographic shadow camera;
+                                  more than RTM_MAX_SPHERES spheres outside the binned sphere path) */
 #define RTM_ERR_HIP -3         /* a HIP runtime call failed */
 #define RTM_ERR_NO_DEVICE -4   /* no usable gfx950 device */
 #define RTM_ERR_OOM -5         /* device allocation failed */
@@ -160,7 +172,8 @@ typedef struct rtm_sdf {
  * Circle planes and capped cylinders are ray traced into the eye viewport after
  * its rasterize (processRaytracingRays, main.rs:569-642); the reference never
  * traces them into the shadow map (main.rs:998-1003).  ABI v2 added the
- * primitive fields, v3 the SDFs. */
+ * primitive fields, v3 the SDFs.  n_spheres may reach RTM_MAX_SCENE_SPHERES (ABI v12, see
+ * the limits above); past it, and for an id outside [0, n_spheres), RTM_ERR_INVALID. */
 typedef struct rtm_scene {
     const rtm_sphere* spheres;
     const rtm_patch* patches;
@@ -261,6 +274,8 @@ int rtm_ctx_last_lanes(rtm_ctx* ctx, int32_t* lanes);
  * rtm_ctx_last_batch: frames per launch of the last call. */
 int rtm_ctx_set_batch(rtm_ctx* ctx, int32_t frames);
 int rtm_ctx_last_batch(rtm_ctx* ctx, int32_t* frames);
+/* (A sequence holding a scene of more than RTM_MAX_SPHERES spheres runs one frame per
+ * launch on one lane; rtm_ctx_last_batch and rtm_ctx_last_lanes then report 1.) */
 
 /* ---- whole frame, host output (blocking) ----
  * Equivalent of: shadow viewport (ORTHO, face BACK, zBuffer=+INF) rasterize +
@@ -271,7 +286,8 @@ int rtm_ctx_last_batch(rtm_ctx* ctx, int32_t* frames);
  * PERSPECTIVE (spheres then project through nalgebra's Perspective3 and
  * projectSphere, main.rs:473-530, 2796-2837, with the aspect 512/512
  * generalised to width/height).  out_rgba: width*height*4 floats. Uses a
- * per-thread default context on device 0. */
+ * per-thread default context on device 0.  At most RTM_MAX_SPHERES spheres (more:
+ * RTM_ERR_INVALID, as before ABI v12; rtm_render_ex renders such a scene). */
 int rtm_render(const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow,
                int32_t width, int32_t height, int32_t march_steps, int32_t flags,
                float* out_rgba);
@@ -280,7 +296,8 @@ int rtm_render(const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* 
  * each evaluating the shadow texels it reads (RTM_FLAG_FUSED_SHADOW when
  * n_gpus > 1: same image bits), each copied from its device straight into its
  * slice of out_rgba.  Blocking.  n_gpus in [1, rtm_device_count()].  (The
- * one-process-per-GPU form is rtm_render_async per rank, see bench.py.) */
+ * one-process-per-GPU form is rtm_render_async per rank, see bench.py.)  At most
+ * RTM_MAX_SPHERES spheres (more: RTM_ERR_UNSUPPORTED; rtm_render_multi_ex likewise). */
 int rtm_render_multi(const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow,
                      int32_t width, int32_t height, int32_t march_steps, int32_t flags,
                      float* out_rgba, int32_t n_gpus);
@@ -290,7 +307,8 @@ int rtm_render_multi(const rtm_scene* scene, const rtm_camera* eye, const rtm_ca
  * registered with rtm_host_register are written by direct DMA from each device
  * (rtm_render_multi_ex: the devices' copies run side by side on their own PCIe
  * links); unregistered (pageable) buffers are copied through the runtime's
- * staging, one host thread per device. */
+ * staging, one host thread per device.  rtm_render_ex takes up to RTM_MAX_SCENE_SPHERES
+ * spheres (the binned sphere path, see the limits). */
 int rtm_render_ex(const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow, int32_t width,
                   int32_t height, int32_t march_steps, int32_t flags, int32_t format, void* out_host);
 int rtm_render_multi_ex(const rtm_scene* scene, const rtm_camera* eye, const rtm_camera* shadow,
@@ -308,7 +326,10 @@ int rtm_host_unregister(void* ptr);
 /* ---- whole frame, device output (asynchronous on ctx's stream) ----
  * Renders eye rows [row_begin, row_end) into out_rgba_dev (device memory,
  * (row_end-row_begin)*width*4 floats, row-major, row 0 = row_begin).  The
- * shadow map is full size unless RTM_FLAG_FUSED_SHADOW. */
+ * shadow map is full size unless RTM_FLAG_FUSED_SHADOW.  More than RTM_MAX_SPHERES
+ * spheres (rtm_render_rows_async too): the binned sphere path, which bins the whole frame
+ * for any row range, stores an f64 shadow map and serves RTM_FLAG_FUSED_SHADOW by
+ * materialising the map (the same image bits). */
 int rtm_render_async(rtm_ctx* ctx, const rtm_scene* scene, const rtm_camera* eye,
                      const rtm_camera* shadow, int32_t width, int32_t height,
                      int32_t march_steps, int32_t flags, int32_t row_begin, int32_t row_end,
@@ -330,7 +351,10 @@ int rtm_render_rows_async(rtm_ctx* ctx, const rtm_scene* scene, const rtm_camera
  * and march_steps) are shared by all lanes: when a frame's tables differ from the
  * previous frame's, the host waits for every lane's earlier work before rebuilding
  * them, so a sequence whose patches change from frame to frame serialises the
- * call (still correct, no longer asynchronous). */
+ * call (still correct, no longer asynchronous).  Frames of more than RTM_MAX_SPHERES
+ * spheres take the binned sphere path and frames of fewer the kernel-argument path, each
+ * its own, in one sequence; such a sequence runs one frame per launch on one lane, and
+ * stays asynchronous (each frame's tables and lists take a slot of a ring of buffers). */
 int rtm_render_frames_async(rtm_ctx* ctx, int32_t n_frames, const rtm_scene* scenes,
                             const rtm_camera* eye, const rtm_camera* shadow, int32_t width,
                             int32_t height, int32_t march_steps, int32_t flags,
@@ -340,13 +364,14 @@ int rtm_render_frames_async(rtm_ctx* ctx, int32_t n_frames, const rtm_scene* sce
  * map (which source won each texel, 1 or 2 bytes) unless
  * RTM_SMAP=f64: this call then decodes it into an f64 buffer of the context on
  * its stream and waits (blocking), so the values are the shadow viewport's
- * zBuffer bit for bit either way. */
+ * zBuffer bit for bit either way.  (The binned sphere path stores f64.) */
 const double* rtm_ctx_shadow_map(rtm_ctx* ctx);
 /* ABI v7: bytes per texel the last non-fused frame's shadow pass stored: 8 (f64),
  * 2 or 1 (coded map); 0 before any, and 0 after a frame with RTM_FLAG_NO_MARCH |
  * RTM_FLAG_NO_SHADOW_RASTER: its shadow viewport is all +INF, so no shadow pass runs
  * (the eye pass evaluates its +INF texels on demand; rtm_ctx_shadow_map still
- * returns the +INF map). */
+ * returns the +INF map).  The binned sphere path always runs its shadow pass and stores
+ * f64: 8 after any of its frames, those two flags included. */
 int32_t rtm_ctx_shadow_map_texel_bytes(rtm_ctx* ctx);
 /* ABI v11: bytes the last non-fused frame's shadow pass stored.  A 1-byte map written by
  * the coded tile stores a span of 64 rows of a column whose march codes are one monotone
@@ -364,9 +389,26 @@ int rtm_ctx_frames_plan(rtm_ctx* ctx, int32_t width, int32_t rows, int32_t n_fra
 /* ABI v11: the eye pass's wave shape in the last frame or batch this context launched:
  * 0 = 64 x 1-pixel rows, 1 = 8 x 8-pixel blocks (small ray-traced frames). */
 int rtm_ctx_last_eye_blocks(rtm_ctx* ctx, int32_t* blocks);
+/* ABI v12: the sphere path of the last frame this context launched: 0 = kernel arguments
+ * (at most RTM_MAX_SPHERES spheres), 1 = binned device lists. */
+int rtm_ctx_last_sphere_path(rtm_ctx* ctx, int32_t* binned);
+/* ABI v12: the list entries the device binner wrote for the last binned frame, per
+ * viewport (0, 0 before any); equal to the sums of rtm_bin_plan's counts on a correct
+ * library.  Blocking. */
+int rtm_ctx_last_bin_refs(rtm_ctx* ctx, int64_t* eye_refs, int64_t* shadow_refs);
+/* ABI v12: the binner's plan for one ORTHOGONAL camera of a width x height viewport: the
+ * tile shape, and per tile in row-major order (*n_tiles = ceil(width / *tile_w) *
+ * ceil(height / *tile_h)) how many spheres the render puts in that tile's list -- the
+ * spheres whose pixel-index ranges reach the tile, a superset of those covering a pixel of
+ * it.  If capacity < *n_tiles only *n_tiles and the tile shape are written.  The code the
+ * render path calls; host only (no context, no device), for any sphere count up to
+ * RTM_MAX_SCENE_SPHERES. */
+int rtm_bin_plan(const rtm_scene* scene, const rtm_camera* cam, int32_t width, int32_t height, int32_t* tile_w,
+                 int32_t* tile_h, int32_t* counts, int64_t capacity, int64_t* n_tiles);
 
 /* Counting variant of the frame (separate, untimed kernels): the per-pass
- * work counts behind the roofline's algorithmic flop count. */
+ * work counts behind the roofline's algorithmic flop count.  At most RTM_MAX_SPHERES
+ * spheres (more: RTM_ERR_UNSUPPORTED). */
 int rtm_render_stats(rtm_ctx* ctx, const rtm_scene* scene, const rtm_camera* eye,
                      const rtm_camera* shadow, int32_t width, int32_t height,
                      int32_t march_steps, int32_t flags, rtm_stats* out);
@@ -378,7 +420,8 @@ int rtm_render_stats(rtm_ctx* ctx, const rtm_scene* scene, const rtm_camera* eye
  * the shadow texels it reads: RTM_FLAG_FUSED_SHADOW, same image bits), and ONE
  * gather (ncclSend/ncclRecv in one ncclGroupStart/End, rccl.h:700-745: RCCL's own
  * ncclGather is this same pattern, but needs equal counts and the last band may
- * be short) assembles the frame in the root's device buffer.  The root renders
+ * be short) assembles the frame in the root's device buffer.  (Every group render call
+ * takes at most RTM_MAX_SPHERES spheres; more: RTM_ERR_UNSUPPORTED.)  The root renders
  * its own band in place; the other ranks' bands go through double-buffered
  * device staging on a communication stream, so frame i+1 renders while frame i
  * is in flight.  RCCL is loaded at the first group call (librccl.so.1; the copy
@@ -464,7 +507,8 @@ int rtm_group_frames_plan(rtm_group* g, int32_t width, int32_t height, int32_t n
                           int32_t* frames_per_chunk, int32_t* lanes);
 /* ABI v9: part `part` of n_parts of the frame under stripe_rows-row cyclic stripes
  * (the rows a group rank renders), compact rows into out_dev (rtm_stripe_rows(...)
- * rows), on ctx's stream; rtm_stripe_rows: that row count (-1: bad arguments). */
+ * rows), on ctx's stream; rtm_stripe_rows: that row count (-1: bad arguments).  At most
+ * RTM_MAX_SPHERES spheres (more: RTM_ERR_UNSUPPORTED). */
 int rtm_render_stripes_async(rtm_ctx* ctx, const rtm_scene* scene, const rtm_camera* eye,
                              const rtm_camera* shadow, int32_t width, int32_t height, int32_t march_steps,
                              int32_t flags, int32_t format, int32_t stripe_rows, int32_t n_parts, int32_t part,
@@ -509,7 +553,8 @@ int rtm_viewport_create(rtm_ctx* ctx, int32_t width, int32_t height, int32_t fac
 void rtm_viewport_destroy(rtm_viewport* vp);
 /* Viewport::rasterize (main.rs:445): ORTHOGONAL (main.rs:452-471) or
  * PERSPECTIVE (main.rs:473-524) projection of every sphere, then
- * rasterizeSphere into the viewport's zBuffer / G-buffer. */
+ * rasterizeSphere into the viewport's zBuffer / G-buffer.  The staged calls take at most
+ * RTM_MAX_SPHERES spheres (more: RTM_ERR_UNSUPPORTED, rtm_render_color_image too). */
 int rtm_viewport_rasterize(rtm_viewport* vp, const rtm_scene* scene);
 /* Viewport::processRaytracingRays (main.rs:569-642): every pixel's camera ray
  * against the circle planes, then the capped cylinders, in scene order; a hit

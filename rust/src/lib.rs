@@ -84,6 +84,9 @@ impl Context {
     /// eye viewport rasterize + processRaytracingRays, renderColorImage (main.rs:1568-1628)
     /// -- as its `Map2d<Color32>`: width*height RGBA f32 in row order, in host memory.
     /// Blocking.  The same frame as rtm_render, on this context's device and stream.
+    /// Limits (rtm.h): up to RTM_MAX_SPHERES spheres with either eye camera and every
+    /// primitive kind; up to RTM_MAX_SCENE_SPHERES spheres with an ORTHOGONAL eye, patches
+    /// and no traced primitives (the binned sphere path; otherwise RTM_ERR_UNSUPPORTED).
     pub fn render(&self, scene: &Scene, eye: &Camera, shadow: &Camera, width: i32, height: i32,
                   march_steps: i32, flags: i32) -> Result<Vec<f32>, Error> {
         if width <= 0 || height <= 0 {

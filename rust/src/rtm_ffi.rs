@@ -1,4 +1,4 @@
-//! Raw bindings of `include/rtm.h` (librtm.so, RTM_ABI_VERSION 11) for the
+//! Raw bindings of `include/rtm.h` (librtm.so, RTM_ABI_VERSION 12) for the
 //! PtrMan/2018RustRayTracer crate.  Every function and struct of the header is
 //! bound here, in header order; `tests/test_rust_ffi.py` parses this file and the
 //! header and fails on any drift (names, argument counts and C types, return types,
@@ -9,10 +9,12 @@
 
 use std::os::raw::{c_char, c_void};
 
-pub const RTM_ABI_VERSION: i32 = 11;
+pub const RTM_ABI_VERSION: i32 = 12;
 
-// limits: scene constants travel as kernel arguments
+// limits: up to RTM_MAX_SPHERES spheres the scene constants travel as kernel arguments;
+// more, up to RTM_MAX_SCENE_SPHERES, render on the binned sphere path (rtm.h, limits)
 pub const RTM_MAX_SPHERES: i32 = 16;
+pub const RTM_MAX_SCENE_SPHERES: i32 = 65536;
 pub const RTM_MAX_PATCHES: i32 = 4;
 pub const RTM_MAX_CIRCLE_PLANES: i32 = 16;
 pub const RTM_MAX_CAPPED_CYLINDERS: i32 = 16;
@@ -219,6 +221,10 @@ extern "C" {
     pub fn rtm_ctx_frames_plan(ctx: *mut rtm_ctx, width: i32, rows: i32, n_frames: i32, lanes: *mut i32,
                                frames_per_launch: *mut i32) -> i32;
     pub fn rtm_ctx_last_eye_blocks(ctx: *mut rtm_ctx, blocks: *mut i32) -> i32;
+    pub fn rtm_ctx_last_sphere_path(ctx: *mut rtm_ctx, binned: *mut i32) -> i32;
+    pub fn rtm_ctx_last_bin_refs(ctx: *mut rtm_ctx, eye_refs: *mut i64, shadow_refs: *mut i64) -> i32;
+    pub fn rtm_bin_plan(scene: *const rtm_scene, cam: *const rtm_camera, width: i32, height: i32, tile_w: *mut i32,
+                        tile_h: *mut i32, counts: *mut i32, capacity: i64, n_tiles: *mut i64) -> i32;
     pub fn rtm_render_stats(ctx: *mut rtm_ctx, scene: *const rtm_scene, eye: *const rtm_camera,
                             shadow: *const rtm_camera, width: i32, height: i32, march_steps: i32, flags: i32,
                             out: *mut rtm_stats) -> i32;
