@@ -28,11 +28,17 @@ def no_out_of_range_reads(rtm, gpu_ctx):
 _oracle_cache = {}
 
 
-def want(oracle, scenes, key, scene, w, h, k=K, flags=0):
-    """The oracle frame + shadow map of a named case, computed once per session."""
-    key = (key, w, h, k, flags)
+def _cam_key(cam):
+    return None if cam is None else (tuple(cam.position), tuple(cam.dirNormalized), tuple(cam.upNormalized),
+                                     tuple(cam.sideNormalized))
+
+
+def want(oracle, scenes, key, scene, w, h, k=K, flags=0, eye=None, sh=None):
+    """The oracle frame + shadow map of a named case, computed once per session (eye, sh:
+    other cameras than eye_camera() and shadow_camera())."""
+    key = (key, w, h, k, flags, _cam_key(eye), _cam_key(sh))
     if key not in _oracle_cache:
-        r = oracle.render(scene, scenes.eye_camera(), scenes.shadow_camera(), w, h, k, flags, nthreads=NT,
+        r = oracle.render(scene, eye or scenes.eye_camera(), sh or scenes.shadow_camera(), w, h, k, flags, nthreads=NT,
                           want_shadow=True)
         r["rgba"].setflags(write=False)
         r["shadow"].setflags(write=False)
@@ -40,18 +46,19 @@ def want(oracle, scenes, key, scene, w, h, k=K, flags=0):
     return _oracle_cache[key]
 
 
-def render(gpu_ctx, scenes, scene, w, h, k=K, flags=0):
+def render(gpu_ctx, scenes, scene, w, h, k=K, flags=0, eye=None, sh=None):
     import torch
     out = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
-    gpu_ctx.render_async(scene, scenes.eye_camera(), scenes.shadow_camera(), w, h, k, flags, out.data_ptr())
+    gpu_ctx.render_async(scene, eye or scenes.eye_camera(), sh or scenes.shadow_camera(), w, h, k, flags,
+                         out.data_ptr())
     gpu_ctx.synchronize()
     return out.cpu().numpy()
 
 
-def check(gpu_ctx, oracle, scenes, key, scene, w, h, k=K, flags=0, path=1):
-    ref = want(oracle, scenes, key, scene, w, h, k, flags)
-    got = render(gpu_ctx, scenes, scene, w, h, k, flags)
+def check(gpu_ctx, oracle, scenes, key, scene, w, h, k=K, flags=0, path=1, eye=None, sh=None):
+    ref = want(oracle, scenes, key, scene, w, h, k, flags, eye, sh)
+    got = render(gpu_ctx, scenes, scene, w, h, k, flags, eye, sh)
     assert gpu_ctx.last_sphere_path() == path
     assert bits_equal(got, ref["rgba"]), first_mismatch(got, ref["rgba"])
     smap = device_smap(gpu_ctx, w, h)

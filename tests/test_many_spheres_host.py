@@ -3,6 +3,7 @@ sizes and fills its per-tile sphere lists from -- checked against the oracle's o
 rasterizer, its treatment of spheres that cover nothing, validation without a device,
 and one golden hash that pins scenes.sphere_field and the oracle on this platform."""
 import ctypes as C
+import dataclasses
 import hashlib
 import json
 import math
@@ -15,24 +16,24 @@ W, H = 200, 136
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "many_spheres.json")
 
 
-def _covered(oracle, scenes, sphere, cam):
+def _covered(oracle, scenes, sphere, cam, w=W, h=H):
     """Pixels the oracle's rasterizer covers with `sphere` alone (either face)."""
     one = scenes.Scene([scenes.PrimitiveSphere(0, sphere.shading, sphere.pos, sphere.r)], [])
-    m = np.zeros((H, W), bool)
+    m = np.zeros((h, w), bool)
     for face in (scenes.EnumFace.FRONT, scenes.EnumFace.BACK):
-        vp = oracle.Viewport(W, H, face, cam)
+        vp = oracle.Viewport(w, h, face, cam)
         vp.rasterize(one)
         m |= np.isfinite(vp.zbuffer())
     return m
 
 
-def _cover_counts(oracle, scenes, scene, cam, tw, th, shape):
+def _cover_counts(oracle, scenes, scene, cam, tw, th, shape, w=W, h=H):
     """Per tile: the spheres covering a pixel of it, and the spheres whose covered
     bounding box, grown by one tile on every side, reaches it."""
     cover = np.zeros(shape, np.int64)
     box = np.zeros(shape, np.int64)
     for s in scene.spherePrimitives:
-        ys, xs = np.nonzero(_covered(oracle, scenes, s, cam))
+        ys, xs = np.nonzero(_covered(oracle, scenes, s, cam, w, h))
         if len(ys) == 0:
             continue
         for ty, tx in set(zip((ys // th).tolist(), (xs // tw).tolist())):
@@ -41,21 +42,103 @@ def _cover_counts(oracle, scenes, scene, cam, tw, th, shape):
     return cover, box
 
 
-@pytest.mark.parametrize("cam", ["eye", "shadow"])
-def test_bin_plan_is_conservative_and_culls(rtm, scenes, oracle, cam):
-    camera = scenes.eye_camera() if cam == "eye" else scenes.shadow_camera()
-    scene = scenes.sphere_field(300)
-    (tw, th), counts = rtm.bin_plan(scene, camera, W, H)
-    assert counts.shape == (-(-H // th), -(-W // tw))
-    cover, box = _cover_counts(oracle, scenes, scene, camera, tw, th, counts.shape)
+def moved_eye(scenes):
+    """eye_camera() translated off the axes (the rays keep their direction)."""
+    return dataclasses.replace(scenes.eye_camera(), position=(-1.0, 0.13, -0.21))
+
+
+def _camera(scenes, cam):
+    return {"eye": scenes.eye_camera, "shadow": scenes.shadow_camera, "tilted": scenes.tilted_shadow_camera,
+            "moved": lambda: moved_eye(scenes)}[cam]()
+
+
+# (the first two keep the ids they had before the other cameras and sizes joined them)
+_PLAN_CASES = [pytest.param("eye", W, H, id="eye"), pytest.param("shadow", W, H, id="shadow")]
+_PLAN_CASES += [pytest.param(c, w, h, id=f"{c}-{w}x{h}") for w, h in ((W, H), (65, 9), (4097, 3))
+                for c in ("eye", "shadow", "tilted", "moved") if (w, h) != (W, H) or c in ("tilted", "moved")]
+
+
+@pytest.mark.parametrize("cam,w,h", _PLAN_CASES)
+def test_bin_plan_is_conservative_and_culls(rtm, scenes, oracle, cam, w, h):
+    camera = _camera(scenes, cam)
+    old = (w, h) == (W, H) and cam in ("eye", "shadow")
+    scene = scenes.sphere_field(300 if old else 120)
+    (tw, th), counts = rtm.bin_plan(scene, camera, w, h)
+    assert counts.shape == (-(-h // th), -(-w // tw))
+    cover, box = _cover_counts(oracle, scenes, scene, camera, tw, th, counts.shape, w, h)
     assert cover.sum() > 0
     assert (counts >= cover).all(), "a tile's list misses a sphere that covers a pixel of it"
-    # the cull must bite: the bound holds for the reference's own bounding boxes plus a
-    # tile of margin (checked here, so the bound is not one only the plan could meet)
-    bound = len(scene.spherePrimitives) * counts.size / 4
-    assert box.sum() < bound
-    assert counts.sum() < bound
+    if old:
+        # the cull must bite: the bound holds for the reference's own bounding boxes plus a
+        # tile of margin (checked here, so the bound is not one only the plan could meet)
+        bound = len(scene.spherePrimitives) * counts.size / 4
+        assert box.sum() < bound
+        assert counts.sum() < bound
     assert counts.sum() <= box.sum()
+
+
+def test_single_spheres_of_every_scale_are_in_their_tiles(rtm, scenes, oracle):
+    """A seeded loop of one-sphere scenes, |r| from 1e-4 to 3 and either sign, centres at
+    random, on pixel sample points and on tile corners (a sphere far smaller than a pixel
+    covers the one pixel whose sample point it sits on): every pixel the oracle covers
+    lies in a tile whose count is 1."""
+    u = scenes.splitmix64(0x51)
+    S = scenes.Shading(1.0, 1.0, 1.0)
+    covering = tiny_covering = 0
+    for case in range(30):
+        cam_name = ("eye", "shadow")[case % 2]
+        cam = _camera(scenes, cam_name)
+        r = 10.0 ** (-4.0 + (math.log10(3.0) + 4.0) * next(u)) * (-1.0 if next(u) < 0.5 else 1.0)
+        kind = case % 3
+        if kind == 0:
+            sx, sy = -0.95 + 1.9 * next(u), -0.95 + 1.9 * next(u)
+        else:  # the NDC of pixel (i, j)'s sample point, (i / W) * 2 - 1; kind 2: a tile's first pixel
+            i, j = int(next(u) * W), int(next(u) * H)
+            if kind == 2:
+                i, j = i // 64 * 64, j // 8 * 8
+            sx, sy = (i / W) * 2.0 - 1.0, (j / H) * 2.0 - 1.0
+        depth = 0.5 * next(u)
+        # screen (x, y) is world (z, y) for the eye and world (x, y) for the sun
+        pos = (depth, sy, sx) if cam_name == "eye" else (sx, sy, 0.5 + depth)
+        sphere = scenes.PrimitiveSphere(0, S, pos, r)
+        covered = _covered(oracle, scenes, sphere, cam)
+        (tw, th), counts = rtm.bin_plan(scenes.Scene([sphere], []), cam, W, H)
+        assert counts.max() <= 1, (case, pos, r)
+        ys, xs = np.nonzero(covered)
+        assert (counts[ys // th, xs // tw] == 1).all(), (case, pos, r)
+        covering += len(ys) > 0
+        tiny_covering += len(ys) > 0 and abs(r) < 0.005  # (half a pixel is 0.005 wide)
+    assert covering >= 20 and tiny_covering >= 3
+
+
+def stack(scenes, n, r):
+    """n spheres, each a little nearer to both cameras than the one before: the last in
+    scene order is the nearest wherever it covers (tests/test_many_spheres_edges.py)."""
+    return scenes.Scene([scenes.PrimitiveSphere(i, scenes.Shading(*scenes._COLORS_B[i % 4]),
+                                                (-1e-3 * i, 0.0, -1e-3 * i), r) for i in range(n)],
+                        [scenes.BENCH_PATCH])
+
+
+@pytest.mark.parametrize("n", [63, 64, 65, 128, 129])
+def test_chunk_seam_stacks_have_n_entries_everywhere(rtm, scenes, n):
+    for cam in (scenes.eye_camera(), scenes.shadow_camera()):
+        counts = rtm.bin_plan(stack(scenes, n, 5.0), cam, W, H)[1]
+        assert counts.shape == (17, 4) and counts.min() == counts.max() == n
+
+
+def refusal_scene(scenes):
+    """65536 spheres over the whole image: at 7680x4320 every one of 64800 tile lists holds
+    them all, more than 2^31-1 entries per viewport."""
+    white = scenes.Shading(1.0, 1.0, 1.0)
+    return scenes.Scene([scenes.PrimitiveSphere(i, white, (0.0, 0.0, 0.0), 5.0) for i in range(65536)],
+                        [scenes.BENCH_PATCH])
+
+
+def test_plan_past_int32_sums_without_wrap(rtm, scenes):
+    counts = rtm.bin_plan(refusal_scene(scenes), scenes.eye_camera(), 7680, 4320)[1]
+    assert counts.shape == (540, 120) and counts.dtype == np.int32
+    assert (counts == 65536).all()
+    assert int(counts.astype(np.int64).sum()) == 64800 * 65536 > 2 ** 31 - 1
 
 
 def test_spheres_that_cover_nothing_are_in_no_list(rtm, scenes, oracle):
